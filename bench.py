@@ -2,6 +2,7 @@
 """Throughput of the U2-Conformer + hybrid CTC-attention training step on MI355X.
 
     python bench.py [--gpus N --steps K --warmup W] [--config small|large|long|tiny]
+                    [--dump-outputs DIR] [--full]
 
 A step = one full training iteration on one synthetic batch per rank: forward, hybrid
 loss, backward, gradient all-reduce (N > 1), clip_grad_norm(5) + NaN-skip + Noam/Adam,
@@ -9,10 +10,14 @@ zero_grad -- the reference's Trainer.run body (liteasr/trainer.py:140-171) with
 accum_grad = 1.  Inputs are resident on the GPU before timing starts.
 
 Prints ONE JSON line (rank 0).  value = utterances/s over all ranks (weak scaling:
-B utterances per rank per step).  Also reports, for the dominant kernel, an achieved
-vs peak roofline measured live with HIP events, and the CPU baseline (the oracle
-restatement, pinned to the reference by tests/test_oracle_golden.py) on a bounded
-sample timed on this host.
+B utterances per rank per step).  A plain run sets up, warms up, times the K steps,
+writes the outputs of the last timed step (--dump-outputs) and prints that line.
+
+--full adds what takes runs of its own: for the dominant kernel an achieved vs peak
+roofline measured live with HIP events (and the committed counter passes of the same
+library build), the CTC kernels, the fixed-chunk leg of a dynamic-chunk config, and the
+CPU baseline (the oracle restatement, pinned to the reference by
+tests/test_oracle_golden.py) on a bounded sample timed on this host.
 """
 
 from __future__ import annotations
@@ -725,6 +730,29 @@ def fixed_chunk_leg(model, net, crit, opt, batch, cfgd, args):
             "utt_per_s": round(cfgd["B"] * args.steps / el, 2)}
 
 
+DUMP_MAX_PARAMS = 4 << 20  # elements of the parameter sample --dump-outputs writes (16 MB of float32)
+
+
+def dump_outputs(path, loss, model, opt_state):
+    """--dump-outputs: what a caller of the timed step holds after its last call, one
+    DIR/<name>.npy each -- `loss` (float32, the value the step returned), `grad_norm` (float64,
+    the norm its clip measured) and `params` (float32, the parameters its update left; above
+    DUMP_MAX_PARAMS elements a fixed, seeded sample of the flat parameter store, in index
+    order).  Model init, batch, dropout and chunk draws are seeded, so two builds run with the
+    same arguments see identical inputs."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    flat = model.store.flat.detach()
+    if flat.numel() > DUMP_MAX_PARAMS:
+        idx = np.sort(np.random.default_rng(1234).choice(flat.numel(), DUMP_MAX_PARAMS, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().cpu().numpy().reshape(1))
+    np.save(os.path.join(path, "grad_norm.npy"), np.asarray([opt_state["grad_norm"]], dtype=np.float64))
+    np.save(os.path.join(path, "params.npy"), flat.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
@@ -738,7 +766,8 @@ def main():
                          "(a chunk size drawn per step on the device, WeNet's distribution), 'none', or a "
                          "fixed chunk size")
     ap.add_argument("--no-chunk-compare", action="store_true",
-                    help="dynamic chunk: skip the second, fixed-c (chunk_size) leg timed after the main one")
+                    help="--full, dynamic chunk: skip the second, fixed-c (chunk_size) leg timed after the "
+                         "main one")
     ap.add_argument("--dropout", type=float, default=0.1)
     ap.add_argument("--graph", default="on", choices=["on", "off"],
                     help="replay the step from hipGraphs (liteasr_amd/graph_step.py) or launch eagerly")
@@ -758,8 +787,15 @@ def main():
                          "implies --graph off (ranges are host-side launch spans)")
     ap.add_argument("--force-ddp", action="store_true",
                     help="wrap in the DDP reducer even at N=1 (world-1 RCCL group; profiling the overlap)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                         "(dump_outputs: loss, grad_norm, params)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the kernel rooflines, the CTC kernels, the "
+                         "fixed-chunk leg of a dynamic-chunk config and the CPU baseline, and look up the "
+                         "committed counter passes (each can be switched off below)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the rooflines and the CTC kernels")
     ap.add_argument("--roofline-only", type=int, default=0, metavar="N",
                     help="only launch the roofline kernel N times (for rocprofv3 --pmc passes)")
     ap.add_argument("--roofline-case", default="family", choices=["family", "dw", "hot", "attn"],
@@ -901,6 +937,8 @@ def main():
         "torch.distributed.run" if "TORCHELASTIC_RUN_ID" in os.environ else "env")
     st = opt.device_state()
     utt = world * cfgd["B"] * args.steps / el
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, model, st)
     if rank == 0:
         out = {
             "metric": "utterances/sec (U2-Conformer+CTC, 80-d fbank T≈1000) at 1/2/4/8 MI355X",
@@ -935,8 +973,9 @@ def main():
             out["graph_nodes_per_step"] = step.graph_nodes()
         if args.profile:
             out["config"]["profile"] = "roctx ranges per fused node (eager)"
-        out["mfma_counter"] = pmc_mfma(args.config)
-        if not args.no_roofline:
+        if args.full:  # everything below takes runs (or file reads) of its own
+            out["mfma_counter"] = pmc_mfma(args.config)
+        if args.full and not args.no_roofline:
             fam = dominant_kernel_roofline(cfgd, dev)
             att = attention_roofline(cfgd, dev)
             # `roofline` = the config's dominant family by time per step (12 encoder layers each:
@@ -948,11 +987,11 @@ def main():
                 out["roofline"] = fam
                 out["roofline"]["attention"] = att
             out["ctc"] = ctc_roofline(cfgd, dev)
-        if cfgd.get("dynamic") and args.graph == "on" and not args.no_chunk_compare:
+        if args.full and cfgd.get("dynamic") and args.graph == "on" and not args.no_chunk_compare:
             del step
             out["config"]["chunk_size"]["fixed_chunk_leg"] = fixed_chunk_leg(model, net, crit, opt, batch, cfgd,
                                                                              args)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.config)
         print(json.dumps(out), flush=True)
     if use_ddp:

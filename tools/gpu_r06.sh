@@ -115,14 +115,14 @@ for s in "$@"; do
     kgpu) run timeout -k 10 600 $PYT tests/test_kernels_gpu.py tests/test_row_ln_gpu.py > "$OUT/kgpu.log" 2>&1 ;;
     model) run timeout -k 10 900 $PYT tests/test_model_gpu.py tests/test_nodes_gpu.py -s > "$OUT/model.log" 2>&1 ;;
     smoke) run timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 ;;
-    bench) run timeout -k 10 400 python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" ;;
+    bench) run timeout -k 10 400 python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" ;;
     benchprof) # rocprofv3 --kernel-trace --stats of the default bench command (the summary kept under profiles/)
            cd /tmp && run timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/benchprof" -o run -- python3 "$R/bench.py" > "$OUT/rocprofv3_bench.log" 2>&1
            grep "^{" "$OUT/rocprofv3_bench.log" | tail -1 > "$OUT/rocprofv3_bench.json"
            cp "$(find "$OUT/benchprof" -name '*kernel_stats.csv' | head -1)" "$OUT/rocprofv3_kernel_stats_bench.csv"; rm -rf "$OUT/benchprof" ;;
     benchq) run timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-roofline --steps 40 > "$OUT/benchq.json" 2> "$OUT/benchq.err" ;;
-    long) run timeout -k 10 300 python3 bench.py --config long --no-cpu-baseline > "$OUT/bench_long.json" 2> "$OUT/bench_long.err" ;;
-    large) run timeout -k 10 400 python3 bench.py --config large --no-cpu-baseline > "$OUT/bench_large.json" 2> "$OUT/bench_large.err" ;;
+    long) run timeout -k 10 300 python3 bench.py --full --config long --no-cpu-baseline > "$OUT/bench_long.json" 2> "$OUT/bench_long.err" ;;
+    large) run timeout -k 10 400 python3 bench.py --full --config large --no-cpu-baseline > "$OUT/bench_large.json" 2> "$OUT/bench_large.err" ;;
     ddp1) run timeout -k 10 300 python3 bench.py --force-ddp --no-cpu-baseline --no-roofline > "$OUT/bench_ddp1.json" 2> "$OUT/bench_ddp1.err" ;;
     ddpab) # world-1 A/B in one call: plain step, torch DDP, native DDP (no collective at world 1),
            # native DDP with the 1-rank RCCL all-reduces forced (their cost beside the backward)
