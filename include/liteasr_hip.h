@@ -666,6 +666,65 @@ int lasr_logsoftmax_topk(const void* logits, int dtype, int64_t rows, int V, int
                          const int32_t* gather_idx, float* topk_val, int32_t* topk_idx,
                          float* gathered, void* stream);
 
+/* ---- Transducer beam search (liteasr/models/transducer.py:137-206) ------------------
+ * The reference's search for one utterance, kept on the device: per expansion the popped
+ * hypothesis' LSTM step (nets/rnn_decoder.py:45-64, memoised by yseq, transducer.py:155-165),
+ * the joint + log_softmax + topk(10) (transducer.py:167-172), the list updates
+ * (transducer.py:174-201) and the next pop (transducer.py:152-153); after the last frame
+ * the best normalised hypothesis (transducer.py:203-206).  Beam 10, blank 0.
+ *
+ * Weights: embed [V][dec_dim] fp32; per layer Wih [4H][in], Whh [4H][H] in w_dtype
+ * (LASR_F32 / LASR_BF16) and bih, bhh [4H] fp32; Wd [J][H], Wj [V][J] in w_dtype, bj [V]
+ * fp32; enc_proj [Tcap][J] fp32 = lin_enc(h) of the utterance (rows >= T' unused).
+ * 11 <= V <= 16000 (the row is staged in LDS); (dec_dim + H) and J floats must fit 64 KiB.
+ *
+ * arena: 256-B aligned device scratch of lasr_rnnt_search_workspace(...) bytes, sections
+ * in this order, each rounded up to 256 B (beam = 10):
+ *   ctrl    64 int32: [0] error (0 ok, 1 node arena full, 2 state slots full, 3 hash full,
+ *           4 non-finite logits, 5 empty list), [1] expansions done, [2] T', [3] popped node,
+ *           [4] its step is not memoised, [5] |A| physical, [6] |A| live, [7] |B|, [8] nodes,
+ *           [9] state slots, [10] LSTM steps executed, [11] done, [12] result node,
+ *           [13] result length, [16-17] popped score (double), [18-19] result score (double)
+ *   cand    16 float log-probs + 16 int32 tokens of the last expansion: the 10 best
+ *           non-blank in descending order (ties: smaller token), then blank at [10]
+ *   yseq    (10 Tcap + 2) int32: the result's tokens, leading 0 included
+ *   lists   (110 + 10) x {double score, int32 node, int32 live}: A then B
+ *   trace   10 Tcap x {double score, int32 node, int32 |A| live at the pop}
+ *   nodes   node_cap x {int32 parent, token, length, state slot or -1}
+ *   hash    hash_cap int32, hash_cap = the power of two >= max(64, 2 node_cap)
+ *   logits  V float
+ *   slots   slot_cap x slot_floats float, slot_floats = (2 layers H + J) rounded up to 64:
+ *           h [layers][H], c [layers][H], lin_dec(h_top) [J]
+ * node_cap / slot_cap <= 0 in lasr_rnnt_search_workspace: the worst case 100 Tcap + 1 /
+ * 10 Tcap + 1 (the args struct takes the resolved values).  Running out of an arena sets
+ * ctrl[0]; the remaining launches of the utterance then do nothing.
+ *
+ * lasr_rnnt_search_init: one launch; empties the trie and pops the root hypothesis [0].
+ * lasr_rnnt_search_expand: the launches of ONE expansion (layers + 3), graph-capturable;
+ * call 10 T' times.  mode 0: the whole search.  mode 1 (host-loop driver for tests and
+ * tools): the caller sets ctrl[1], ctrl[3], ctrl[4] and the node records; the kernels run
+ * the step / joint and stop after writing cand. */
+#define LASR_RNNT_SEARCH_MAX_LAYERS 8
+typedef struct lasr_rnnt_search_args {
+  int Tcap, layers, dec_dim, H, J, V;
+  int node_cap, slot_cap;
+  int w_dtype;
+  void* arena;
+  int64_t arena_bytes;
+  const float* embed;
+  const void* Wih[LASR_RNNT_SEARCH_MAX_LAYERS];
+  const void* Whh[LASR_RNNT_SEARCH_MAX_LAYERS];
+  const float* bih[LASR_RNNT_SEARCH_MAX_LAYERS];
+  const float* bhh[LASR_RNNT_SEARCH_MAX_LAYERS];
+  const void* Wd;
+  const void* Wj;
+  const float* bj;
+  const float* enc_proj;
+} lasr_rnnt_search_args;
+int64_t lasr_rnnt_search_workspace(int Tcap, int layers, int H, int J, int V, int node_cap, int slot_cap);
+int lasr_rnnt_search_init(const lasr_rnnt_search_args* a, int Tp, void* stream);
+int lasr_rnnt_search_expand(const lasr_rnnt_search_args* a, int mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

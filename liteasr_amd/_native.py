@@ -99,6 +99,24 @@ class ReduceSeg(C.Structure):
                 ("split", _l)]
 
 
+RNNT_SEARCH_MAX_LAYERS = 8
+
+
+class RnntSearchArgs(C.Structure):
+    """Mirror of ``lasr_rnnt_search_args``."""
+
+    _fields_ = [
+        ("Tcap", _i), ("layers", _i), ("dec_dim", _i), ("H", _i), ("J", _i), ("V", _i),
+        ("node_cap", _i), ("slot_cap", _i),
+        ("w_dtype", _i),
+        ("arena", _p), ("arena_bytes", _l),
+        ("embed", _p),
+        ("Wih", _p * RNNT_SEARCH_MAX_LAYERS), ("Whh", _p * RNNT_SEARCH_MAX_LAYERS),
+        ("bih", _p * RNNT_SEARCH_MAX_LAYERS), ("bhh", _p * RNNT_SEARCH_MAX_LAYERS),
+        ("Wd", _p), ("Wj", _p), ("bj", _p), ("enc_proj", _p),
+    ]
+
+
 # name -> argtypes (all return int unless listed in _RESTYPES)
 SIGNATURES = {
     "lasr_version": [],
@@ -191,8 +209,12 @@ SIGNATURES = {
     "lasr_spec_augment": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _l, _p],
     "lasr_spec_augment_ws_bytes": [_i, _i],
     "lasr_logsoftmax_topk": [_p, _i, _l, _i, _l, _i, _p, _p, _p, _p, _p],
+    "lasr_rnnt_search_workspace": [_i, _i, _i, _i, _i, _i, _i],
+    "lasr_rnnt_search_init": [C.POINTER(RnntSearchArgs), _i, _p],
+    "lasr_rnnt_search_expand": [C.POINTER(RnntSearchArgs), _i, _p],
 }
 _RESTYPES = {"lasr_last_error": C.c_char_p, "lasr_spec_augment_ws_bytes": C.c_int64,
+             "lasr_rnnt_search_workspace": C.c_int64,
              "lasr_conv2_dx_w1_workspace": C.c_int64, "lasr_attn_split_work": C.c_int64,
              "lasr_dropout_scale": C.c_float}
 

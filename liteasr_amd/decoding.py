@@ -1,4 +1,5 @@
-"""Inference searches of U2 (liteasr/models/u2.py:160-317), SURVEY §8 f3.
+"""Inference searches of U2 (liteasr/models/u2.py:160-317), SURVEY §8 f3, and the Transducer
+beam search (liteasr/models/transducer.py:137-206; device-resident, csrc/rnnt_search.hip).
 
 Device side: the encoder / decoder run through the same HIP kernels as training
 (nets/functional.py: encoder_out, ctc_logits, decoder_logits); per-frame log_softmax +
@@ -201,3 +202,218 @@ def attention_beam_search(model, x, beam=10, trace=None):
         end = hyps[:, -1] == eos
     best = int(np.argmax(scores.reshape(-1)))
     return hyps[best].tolist()
+
+
+# ======================================================= transducer beam search ===
+_BEAM = 10
+_ERRORS = {1: "node arena full", 2: "state-slot arena full", 3: "trie hash full", 4: "non-finite joint logits",
+           5: "empty hypothesis list"}
+# ctrl words of the search arena (include/liteasr_hip.h)
+_C_ERR, _C_POPS, _C_CUR, _C_DOSTEP, _C_STEPS, _C_DONE, _C_BEST, _C_BESTLEN = 0, 1, 3, 4, 10, 11, 12, 13
+
+
+def _rnnt_layout(Tcap, layers, H, J, V, node_cap, slot_cap):
+    """Byte offsets of the arena sections (the formula of include/liteasr_hip.h)."""
+    up = lambda n: -(-n // 256) * 256  # noqa: E731
+    hash_cap = 64
+    while hash_cap < 2 * node_cap:
+        hash_cap *= 2
+    slot_floats = -(-(2 * layers * H + J) // 64) * 64
+    sizes = [("ctrl", 64 * 4), ("cand", 2 * 16 * 4), ("yseq", (_BEAM * Tcap + 2) * 4), ("lists", 120 * 16),
+             ("trace", _BEAM * Tcap * 16), ("nodes", node_cap * 16), ("hash", hash_cap * 4), ("logits", V * 4),
+             ("slots", slot_cap * slot_floats * 4)]
+    off, o = {}, 0
+    for name, n in sizes:
+        off[name] = o
+        o += up(n)
+    off["total"], off["slot_floats"] = o, slot_floats
+    return off
+
+
+class _RnntSearch:
+    """Arena, argument block and the captured frame graph of one model (one parameter
+    generation, one set of capacities)."""
+
+    def __init__(self, model, Tcap, node_cap, slot_cap):
+        dec = model.decoder
+        wd, wj = dec.weights(), model.joint_params.weights()
+        dev = wj.Wj.device
+        self.Tcap, self.layers, self.H = Tcap, dec.n_layer, dec.h_units
+        self.J, self.V = wj.Wd.shape[0], wj.Wj.shape[0]
+        self.node_cap = int(node_cap) if node_cap else _BEAM * _BEAM * Tcap + 1
+        self.slot_cap = int(slot_cap) if slot_cap else _BEAM * Tcap + 1
+        if self.node_cap < 1 or self.slot_cap < 1:
+            raise ValueError("transducer_beam_search: capacities must be positive")
+        self.off = _rnnt_layout(Tcap, self.layers, self.H, self.J, self.V, self.node_cap, self.slot_cap)
+        nbytes = K.rnnt_search_workspace(Tcap, self.layers, self.H, self.J, self.V, self.node_cap, self.slot_cap)
+        assert nbytes == self.off["total"], (nbytes, self.off["total"])
+        self.arena = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        self.enc_proj = torch.zeros(Tcap, self.J, dtype=torch.float32, device=dev)
+        self.weights = (wd, wj)  # keeps the views the argument block points into
+        self.args = K.rnnt_search_args(self.arena, Tcap, self.node_cap, self.slot_cap, wd.E,
+                                       [(l.Wih, l.Whh, l.bih, l.bhh) for l in wd.layers], wj.Wd, wj.Wj, wj.bj,
+                                       self.enc_proj)
+        self.graph = None
+
+    def view(self, name, dtype, count):
+        o = self.off[name]
+        return self.arena[o: o + count * torch.empty((), dtype=dtype).element_size()].view(dtype)
+
+    def start(self, model, h, Tp):
+        """enc_proj = lin_enc(h) for all frames (transducer.py:221), then the init launch."""
+        wj = self.weights[1]
+        K.linear(h, wj.We, self.enc_proj[:Tp], bias=wj.be)
+        K.rnnt_search_init(self.args, Tp)
+
+    def frame_graph(self):
+        """The launches of one frame (10 expansions), captured once as a linear hipGraph; the
+        frame index advances on the device, so the same graph serves every frame and T'."""
+        if self.graph is None:
+            cur = torch.cuda.current_stream()
+            side = torch.cuda.Stream()
+            side.wait_stream(cur)
+            with torch.cuda.stream(side):  # warm-up: code objects loaded before the capture
+                K.rnnt_search_init(self.args, 1)
+                for _ in range(_BEAM):
+                    K.rnnt_search_expand(self.args, 0)
+            cur.wait_stream(side)
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                for _ in range(_BEAM):
+                    K.rnnt_search_expand(self.args, 0)
+            self.graph = g
+        return self.graph
+
+    def pops(self, n):
+        """The first n pops as [(yseq tuple, score, |A|)] (reads the trace and the trie)."""
+        tr = self.view("trace", torch.int32, 4 * n).cpu().numpy().reshape(n, 4)
+        score = np.ascontiguousarray(tr[:, :2]).view(np.float64).reshape(n)
+        nodes = self.view("nodes", torch.int32, 4 * self.node_cap).cpu().numpy().reshape(-1, 4)
+        memo, out = {-1: ()}, []
+
+        def yseq(k):
+            if k not in memo:
+                memo[k] = yseq(int(nodes[k, 0])) + (int(nodes[k, 1]),)
+            return memo[k]
+
+        for j in range(n):
+            out.append((yseq(int(tr[j, 2])), float(score[j]), int(tr[j, 3])))
+        return out
+
+
+def _rnnt_search_state(model, x, Tp, node_cap, slot_cap):
+    if x.device.type != "cuda":
+        raise RuntimeError("liteasr_amd decoding runs on the HIP device only")
+    if x.dim() != 3 or x.shape[0] != 1:
+        raise ValueError("transducer_beam_search: one utterance x [1, T, F]")
+    if model.vocab_size < _BEAM + 1:
+        raise ValueError(f"transducer_beam_search: vocab_size {model.vocab_size} < 11 (topk(10) over the non-blank "
+                         "tokens, transducer.py:168)")
+    h, T = encode(model, x)
+    assert T == Tp
+    st = model.store
+    Tcap = 64
+    while Tcap < Tp:
+        Tcap *= 2
+    key = (st.flat._version, st.generation, Tcap, node_cap, slot_cap)
+    cache = model.__dict__.setdefault("_rnnt_search", {})
+    s = cache.get(key)
+    if s is None:
+        cache.clear()
+        s = cache[key] = _RnntSearch(model, Tcap, node_cap, slot_cap)
+    return s, h
+
+
+def _sub_len(T):
+    return ((T - 1) // 2 - 1) // 2
+
+
+def transducer_beam_search(model, x, beam=10, trace=None, node_cap=None, slot_cap=None):
+    """transducer.py:137-206 for one utterance x [1, T, F] (no padding mask): the token list
+    of the best hypothesis, leading blank included.
+
+    The encoder runs through encode(); enc_proj = lin_enc(h) is one GEMM; the search itself
+    (LSTM steps memoised by yseq, joint, log-softmax, top-10, the lists A / B with double
+    scores, the pops) stays on the device: the launches of one frame are a hipGraph replayed
+    T' times, and ONE device-to-host copy per utterance brings back the error flag, the best
+    hypothesis and its tokens.  trace (a dict) receives "pops": [(yseq, score, |A|)] per
+    expansion, and "steps": the LSTM steps actually executed (a device counter).  node_cap /
+    slot_cap: capacities of the trie and of the state slots (default: the worst case
+    100 T'cap + 1 / 10 T'cap + 1); running out raises after the utterance."""
+    if beam != _BEAM:
+        raise ValueError("transducer_beam_search: only the reference's beam of 10 is built")
+    Tp = _sub_len(x.shape[1])
+    if Tp <= 0:
+        return [0]
+    s, h = _rnnt_search_state(model, x, Tp, node_cap, slot_cap)
+    g = s.frame_graph()
+    s.start(model, h, Tp)
+    for _ in range(Tp):
+        g.replay()
+    head = s.arena[: s.off["lists"]].cpu().numpy()  # ctrl, candidates, result tokens
+    ctrl = head[:256].view(np.int32)
+    if ctrl[_C_ERR] != 0:
+        raise RuntimeError(f"transducer_beam_search: {_ERRORS.get(int(ctrl[_C_ERR]), 'error')} "
+                           f"(node_cap {s.node_cap}, slot_cap {s.slot_cap}, T' {Tp})")
+    assert ctrl[_C_DONE] == 1 and ctrl[_C_POPS] == _BEAM * Tp, ctrl[:16]
+    n = int(ctrl[_C_BESTLEN])
+    yseq = head[s.off["yseq"]: s.off["yseq"] + 4 * n].view(np.int32).tolist()
+    if trace is not None:
+        trace["pops"] = s.pops(_BEAM * Tp)
+        trace["steps"] = int(ctrl[_C_STEPS])
+        trace["score"] = float(ctrl[18:20].view(np.float64)[0]) / n
+    return yseq
+
+
+def _transducer_beam_search_hostloop(model, x, trace=None):
+    """The same kernels driven one expansion at a time, with the reference's list logic in
+    Python (one host round trip per expansion).  For tests and tools only: it is the
+    exactness yardstick of the device-resident search, which must agree with it bit for bit.
+    trace additionally receives "cand": per expansion the (log-probs, tokens) the device
+    returned (10 best non-blank, then blank)."""
+    Tp = _sub_len(x.shape[1])
+    if Tp <= 0:
+        return [0]
+    s, h = _rnnt_search_state(model, x, Tp, None, None)
+    s.start(model, h, Tp)
+    ctrl = s.view("ctrl", torch.int32, 64)
+    nodes = s.view("nodes", torch.int32, 4 * s.node_cap).view(-1, 4)
+    cand = s.view("cand", torch.int32, 32)
+    tab = [[-1, 0, 1, -1]]  # parent, token, len, slot
+    child = {}
+    seqs = {0: (0,)}
+    kept, n_slots, steps, pops, cands = [(0, 0.0)], 0, 0, [], []
+    for t in range(Tp):
+        A, B = kept, []
+        while len(B) < _BEAM:
+            i = max(range(len(A)), key=lambda j: A[j][1])
+            pops.append((seqs[A[i][0]], A[i][1], len(A)))
+            node, score = A.pop(i)
+            dostep = tab[node][3] < 0
+            if dostep:
+                tab[node][3] = n_slots
+                n_slots += 1
+                steps += 1
+                nodes[node].copy_(torch.tensor(tab[node], dtype=torch.int32), non_blocking=False)
+            ctrl[1:5].copy_(torch.tensor([_BEAM * t, Tp, node, int(dostep)], dtype=torch.int32))
+            K.rnnt_search_expand(s.args, 1)
+            c = cand.cpu().numpy()
+            vals, toks = c[:16].view(np.float32), c[16:]
+            cands.append((vals[:_BEAM + 1].copy(), toks[:_BEAM + 1].copy()))
+            for j in range(_BEAM):
+                k = (node, int(toks[j]))
+                if k not in child:
+                    child[k] = len(tab)
+                    tab.append([node, k[1], tab[node][2] + 1, -1])
+                    seqs[child[k]] = seqs[node] + (k[1],)
+                A.append((child[k], score + float(vals[j])))
+            B.append((node, score + float(vals[_BEAM])))
+        kept = B
+    norm = [sc / tab[n][2] for n, sc in kept]
+    b = max(range(len(kept)), key=lambda j: norm[j])
+    if int(ctrl[0].item()) != 0:
+        raise RuntimeError("transducer hostloop: device error flag set")
+    if trace is not None:
+        trace["pops"], trace["steps"], trace["score"], trace["cand"] = pops, steps, norm[b], cands
+    return list(seqs[kept[b][0]])

@@ -1137,3 +1137,54 @@ def lstm_cell_bwd(gates, bias, c, c_prev, dh_out, dh_rec, dc_next, dgates, dc_pr
     N.call("lasr_lstm_cell_bwd", ptr(gates), gates.stride(0), ptr(bias), ptr(c), ptr(c_prev), ptr(dh_out),
            dt(dh_out) if dh_out is not None else 0, dh_out.stride(0) if dh_out is not None else 0, ptr(dh_rec),
            ptr(dc_next), B, H, ptr(dgates), dt(dgates), dgates.stride(0), ptr(dc_prev), stream())
+
+
+# -------------------------------------------------- transducer beam search ---
+def rnnt_search_workspace(Tcap, layers, H, J, V, node_cap=0, slot_cap=0):
+    """Arena bytes of the device-resident transducer search (lasr_rnnt_search_workspace;
+    host only).  node_cap / slot_cap <= 0: the worst case 100 Tcap + 1 / 10 Tcap + 1."""
+    return int(N.load().lasr_rnnt_search_workspace(Tcap, layers, H, J, V, node_cap, slot_cap))
+
+
+def rnnt_search_args(arena, Tcap, node_cap, slot_cap, embed, layers, Wd, Wj, bj, enc_proj):
+    """The argument block of lasr_rnnt_search_init / _expand (transducer.py:137-206).
+    layers: [(Wih, Whh, bih, bhh)]; Wih / Whh / Wd / Wj share one dtype (fp32 or bf16), embed,
+    the biases and enc_proj [Tcap, J] are fp32; arena: uint8 tensor of
+    rnnt_search_workspace(...) bytes.  The block holds raw pointers: the caller keeps the
+    tensors alive."""
+    a = N.RnntSearchArgs()
+    H, J, V = layers[0][1].shape[1], Wd.shape[0], Wj.shape[0]
+    if len(layers) > N.RNNT_SEARCH_MAX_LAYERS:
+        raise ValueError(f"rnnt_search: at most {N.RNNT_SEARCH_MAX_LAYERS} LSTM layers")
+    ws = [w for l in layers for w in l[:2]] + [Wd, Wj]
+    if any(w.dtype != Wd.dtype or not w.is_contiguous() for w in ws):
+        raise ValueError("rnnt_search: the weight matrices must be contiguous and share one dtype")
+    f32 = [embed, bj, enc_proj] + [b for l in layers for b in l[2:]]
+    if any(t.dtype != torch.float32 or not t.is_contiguous() for t in f32):
+        raise ValueError("rnnt_search: embed, biases and enc_proj must be contiguous fp32")
+    if tuple(enc_proj.shape) != (Tcap, J) or Wd.shape[1] != H or Wj.shape[1] != J or embed.shape[0] != V:
+        raise ValueError("rnnt_search: inconsistent shapes")
+    if arena.dtype != torch.uint8 or arena.numel() < rnnt_search_workspace(Tcap, len(layers), H, J, V, node_cap,
+                                                                           slot_cap):
+        raise ValueError("rnnt_search: arena too small")
+    a.Tcap, a.layers, a.dec_dim, a.H, a.J, a.V = Tcap, len(layers), embed.shape[1], H, J, V
+    a.node_cap, a.slot_cap, a.w_dtype = node_cap, slot_cap, dt(Wd)
+    a.arena, a.arena_bytes = ptr(arena), arena.numel()
+    a.embed = ptr(embed)
+    for i, (Wih, Whh, bih, bhh) in enumerate(layers):
+        if tuple(Wih.shape) != (4 * H, embed.shape[1] if i == 0 else H) or tuple(Whh.shape) != (4 * H, H):
+            raise ValueError("rnnt_search: inconsistent LSTM shapes")
+        a.Wih[i], a.Whh[i], a.bih[i], a.bhh[i] = ptr(Wih), ptr(Whh), ptr(bih), ptr(bhh)
+    a.Wd, a.Wj, a.bj, a.enc_proj = ptr(Wd), ptr(Wj), ptr(bj), ptr(enc_proj)
+    return a
+
+
+def rnnt_search_init(args, Tp):
+    """Empty trie, root hypothesis [0] popped (one launch)."""
+    N.call("lasr_rnnt_search_init", C.byref(args), Tp, stream())
+
+
+def rnnt_search_expand(args, mode=0):
+    """The launches of one expansion (LSTM layers + lin_dec + joint + finalise); mode 1
+    stops after the candidates (host-loop driver)."""
+    N.call("lasr_rnnt_search_expand", C.byref(args), mode, stream())

@@ -142,6 +142,14 @@ class Transducer(FusedEncoderModel):
         h = FN.TransducerHeadsFn.apply(x, self.lin_jnt.weight, self, env, ids, U1)
         return h.view(B, T, U1, self.vocab_size)
 
+    def inference(self, x):
+        """transducer.py:137-206: beam search (beam 10) over the LSTM prediction network and
+        the tanh joint for one utterance x [1, T, F]; the token list of the best hypothesis,
+        leading blank included.  Device-resident (decoding.transducer_beam_search)."""
+        from ..decoding import transducer_beam_search
+
+        return transducer_beam_search(self, x)
+
     def get_pred_len(self, xlens) -> Tensor:
         """transducer.py:186-188."""
         return super().get_pred_len(xlens)
