@@ -236,9 +236,10 @@ extern "C" int lasr_cif_bwd(const lasr_cif_args* a, void* stream) {
 
 extern "C" int lasr_glancing_mix(int64_t rows, int D, const uint8_t* replace, const float* a, const float* b,
                                  float* out, float* out2, int backward, void* stream) {
-  LASR_CHECK_ARG(rows >= 0 && D > 0 && replace && a && out && (backward ? out2 != nullptr : b != nullptr),
+  LASR_CHECK_ARG(rows >= 0 && D > 0, "lasr_glancing_mix: bad sizes");
+  if (rows == 0) return LASR_OK;  // (empty tensors carry null pointers)
+  LASR_CHECK_ARG(replace && a && out && (backward ? out2 != nullptr : b != nullptr),
                  "lasr_glancing_mix: bad arguments");
-  if (rows == 0) return LASR_OK;
   const int64_t n = rows * D;
   const int nb = (int)std::min<int64_t>((n + 255) / 256, 4096);
   glancing_mix_kernel<<<nb, 256, 0, (hipStream_t)stream>>>(rows, D, replace, a, b, out, out2, backward);
