@@ -231,6 +231,10 @@ def load():
     global _lib
     if _lib is not None:
         return _lib
+    want = os.environ.get("LITEASR_HIP_LIB")  # a label tools/with_lib.py sets, never a selector
+    if want and os.path.abspath(want) != os.path.abspath(LIB_PATH):
+        raise NativeError(f"LITEASR_HIP_LIB={want} does not select the library (this process loads {LIB_PATH}); "
+                          "run `python tools/with_lib.py LIB script.py` to use another build")
     if not os.path.exists(LIB_PATH):
         raise NativeError(
             f"libliteasr_hip.so not found at {LIB_PATH}; build it with `make` "

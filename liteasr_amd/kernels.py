@@ -89,7 +89,12 @@ def deferred_reductions(hold=False, on_done=None):
     run at the end of the block, but its reductions wait in a queue (their partial buffers
     alive) for the next block that does not hold, or flush_reductions(): the reductions of
     several layers then share lasr_reduce_multi launches, each with its usual summation order,
-    and the held blocks' on_done callbacks run after them, in order."""
+    and the held blocks' on_done callbacks run after them, in order.
+
+    Only an outermost block can hold or take a callback (its end is where reductions are
+    launched or queued): asking for either inside another block raises."""
+    if _DEFER.depth and (hold or on_done is not None):
+        raise RuntimeError("deferred_reductions: hold / on_done inside another deferred block would be dropped")
     _DEFER.depth += 1
     ok = False
     try:

@@ -227,7 +227,7 @@ class FusedEncoderModel(LiteasrModel):
             p_ctc=ctc.dropout_rate if ctc is not None else 0.0,  # always on (liteasr/nets/ctc.py:29)
             p_dec=dr.drop, p_dec_ff=dr.ff, p_dec_att=dr.self_att, p_dec_src_att=dr.src_att,
             p_dec_pos=getattr(dr, "pos", 0.0), ys_in=prep.ys_in, dec_mask=prep.dec_mask, mask_k=prep.enc_mask,
-            seed=self._seed_base)
+            seed=self._seed_base, links=None)
         if prep.chunk_mask is not None:
             env.mask, env.msb, env.msq = prep.chunk_mask, prep.chunk_mask.stride(0), prep.chunk_mask.stride(1)
         else:
@@ -248,29 +248,15 @@ class FusedEncoderModel(LiteasrModel):
             K.pe_fwd(None, T, T, d, enc.pe.table(T), 1.0, pos, env.p_pos, env.seed + 4)
             pp = FN.pos_projections(pos, [layer.weights().att.Wpos for layer in enc.enc_layers]) \
                 if FN.BATCH_POS_PROJ else None
-        env.pos_proj = {id(layer): p for layer, p in zip(enc.enc_layers, pp)} if pp else None
-        layers = list(enc.enc_layers)
+        # what the layer nodes hand each other across their boundaries, fresh for this forward
+        env.links = FN.LayerLink.stack(enc.enc_layers, self._seg.cuts if self._seg is not None else (), pp)
         conformer = getattr(enc, "arch", "conformer") == "conformer"
-        env.pre_ln = env.bwd_chain = None
-        # layer nodes that launch the queued parameter-gradient reductions (FN.LAYER_RED_HOLD):
-        # the lowest layer, and the lowest layer of every backward segment (a cut before layer j)
-        seg = self._seg
-        env.red_flush = {id(layers[0])} if layers else set()
-        if seg is not None:
-            env.red_flush |= {id(layers[j]) for j in seg.cuts if 0 <= j < len(layers)}
-        for j, layer in enumerate(layers):
+        for j, layer in enumerate(enc.enc_layers):
             x = self._cut(x, j)
-            if not conformer:  # Transformer layers: no final norm to chain the next first norm into
-                env.next_ln = None
+            if conformer:
+                x = FN.ConformerLayerFn.apply(x, pos, layer.final_norm.weight, layer, env)
+            else:  # Transformer layers: no final norm to chain the next first norm into
                 x = FN.TransformerLayerFn.apply(x, pos, layer.feed_forward_norm.weight, layer, env)
-                continue
-            if j + 1 < len(layers):
-                wn = layers[j + 1].weights().ln_a
-                env.next_ln = (layers[j + 1], wn.g, wn.b)
-            else:
-                env.next_ln = None
-            x = FN.ConformerLayerFn.apply(x, pos, layer.final_norm.weight, layer, env)
-        env.next_ln = env.pre_ln = None
         x = self._cut(x, len(enc.enc_layers))
         return x, prep, env
 

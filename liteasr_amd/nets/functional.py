@@ -14,6 +14,8 @@ Weight gradients never travel through autograd: the backward kernels accumulate 
 (beta = 1) straight into the flat fp32 grad buffer of FlatParams; autograd only
 carries the residual-stream gradient between nodes.  Each node takes one "anchor"
 parameter as an input so that its output requires grad whenever the model does.
+What neighbouring encoder layer nodes hand each other (a chained norm, its gradient, queued
+reductions, the batched positional projection) goes through one LayerLink per layer (links.py).
 
 Storage: residual streams fp32; GEMM operands / activations in the model's compute
 dtype ``adt`` (bf16, or fp32 for the parity build); attention scores fp32.
@@ -22,7 +24,6 @@ dtype ``adt`` (bf16, or fp32 for the parity build); attention scores fp32.
 from __future__ import annotations
 
 import math
-import os
 from types import SimpleNamespace
 
 import torch
@@ -30,6 +31,7 @@ import torch
 from .. import kernels as K
 from .._native import ACT_GATE, ACT_NONE, ACT_RELU, ACT_SWISH, ACT_TANH
 from ..utils.markers import ranged
+from .links import LayerLink
 
 F32 = torch.float32
 LN_EPS = 1e-12
@@ -61,11 +63,12 @@ def ln_forward(x, g, b, adt, y2=False, p2=0.0, seed2=0):
 
 # Full-row GEMM tiles with the next LayerNorm in the epilogue (gemm_row.hip): a residual
 # projection and the norm after it, or an input-gradient GEMM and the norm backward before
-# it, in one launch, bit-identical to the two launches.  LASR_ROW_LN=0 keeps two launches
-# (benchmark A/B); shapes the kernel does not take (fp32 build, other widths) keep them too.
-ROW_LN = os.environ.get("LASR_ROW_LN", "1") != "0"
-# the decoder's norms after / before its attention projections on the row kernel (A/B switch)
-DEC_ROW_LN = os.environ.get("LASR_DEC_ROW_LN", "1") != "0"
+# it, in one launch, bit-identical to the two launches.  False keeps two launches (like every
+# switch here a module attribute that tests and tools/flag_ab.py set; tests/test_switches_gpu.py
+# pins the pair); shapes the kernel does not take (fp32 build, other widths) keep them too.
+ROW_LN = True
+# the decoder's norms after / before its attention projections on the row kernel
+DEC_ROW_LN = True
 # K >= 1024 GEMMs whose plan splits K (the decoder's FFN on B*(L+1) rows) run the following
 # LayerNorm (forward) / the preceding one's backward in their split-K reduction launch
 # (gemm_ln.hip); False: separate launches (tests/test_fusions_gpu.py pins the two bit for bit)
@@ -90,17 +93,35 @@ BN_GLU_FUSED = True
 LAYER_RED_HOLD = True
 
 
-def _red_hold(env, layer):
-    """Whether this encoder layer's backward node may leave its reductions queued: not the
-    last layer node of its backward segment (the model lists those in env.red_flush)."""
-    fl = getattr(env, "red_flush", None)
-    return LAYER_RED_HOLD and fl is not None and id(layer) not in fl
+def _link(env, layer):
+    """The layer's LayerLink of this forward (nets/links.py); None: a standalone node."""
+    return env.links[layer] if env.links is not None else None
 
 
-class PostLN(SimpleNamespace):
+def _hold(link):
+    """Whether a layer's backward node leaves its reductions queued for a layer below it."""
+    return LAYER_RED_HOLD and link is not None and not link.floor
+
+
+class PostLN:
     """A LayerNorm to run on a residual projection's output row in the same launch:
     g, b (its parameters), f32 (y1 stored fp32: a layer's final norm), nxt (optional
     (g2, b2) of a chained second norm, bf16 out).  After the call: y1, m1, r1 (+ y2, m2, r2)."""
+
+    __slots__ = ("g", "b", "f32", "nxt", "y1", "m1", "r1", "y2", "m2", "r2")
+
+    def __init__(self, ln, f32=False, nxt=None):
+        self.g, self.b, self.f32, self.nxt = ln.g, ln.b, f32, nxt
+        self.y1 = self.m1 = self.r1 = self.y2 = self.m2 = self.r2 = None
+
+
+def norm_of(x, ln, adt, post=None):
+    """(y, mean, rstd) of the norm `ln` of x: post's outputs when the residual projection that
+    produced x ran it in its launch (res_proj), else the norm as its own launch."""
+    if post is not None and post.y1 is not None:
+        return post.y1, post.m1, post.r1
+    y, _, m, r = ln_forward(x, ln.g, ln.b, adt)
+    return y, m, r
 
 
 def res_proj(x, W, bias, res, res_scale, p_res, s_res, post=None):
@@ -135,11 +156,18 @@ def res_proj(x, W, bias, res, res_scale, p_res, s_res, post=None):
     return out
 
 
-class LnBwd(SimpleNamespace):
+class LnBwd:
     """The LayerNorm backward that consumes an input-gradient GEMM's output dln (the norm
     in front of a sub-block, liteasr/nets/conformer_layer.py:37-66): x, g (gamma), mean,
     rstd, dx (fp32 out), dgamma, dbeta, and optionally dres (fp32 residual gradient added),
-    gb (+ bscale, bp, bseed: the preceding branch's gradient, layernorm_bwd's gb)."""
+    gb (+ bscale, bp, bseed: the preceding branch's gradient, layernorm_bwd's gb), chain (dx_ln)."""
+
+    __slots__ = ("x", "g", "mean", "rstd", "dx", "dgamma", "dbeta", "dres", "gb", "bscale", "bp", "bseed", "chain")
+
+    def __init__(self, x, g, mean, rstd, dx, dgamma, dbeta, dres=None, gb=None, bscale=1.0, bp=0.0, bseed=0,
+                 chain=None):
+        self.x, self.g, self.mean, self.rstd, self.dx, self.dgamma, self.dbeta = x, g, mean, rstd, dx, dgamma, dbeta
+        self.dres, self.gb, self.bscale, self.bp, self.bseed, self.chain = dres, gb, bscale, bp, bseed, chain
 
 
 def dx_ln(dy, W, lnb):
@@ -149,7 +177,7 @@ def dx_ln(dy, W, lnb):
     right after it -- in the same launch as lnb's (lasr_layernorm2_bwd, lnb.dx never stored)
     when lnb is not on the row kernel."""
     M, D = dy.shape[0], W.shape[1]
-    ch = getattr(lnb, "chain", None) if lnb is not None else None
+    ch = lnb.chain if lnb is not None else None
     if lnb is not None and ROW_LN and K.row_ln_ok(dy, W, D) and lnb.x.dtype == F32 and lnb.dx.dtype == F32:
         K.linear_dx_ln_bwd(dy, W, lnb.x, lnb.g, lnb.mean, lnb.rstd, lnb.dx, lnb.dgamma, lnb.dbeta,
                            dres=lnb.dres, gb=lnb.gb, bscale=lnb.bscale, bp=lnb.bp, bseed=lnb.bseed)
@@ -234,9 +262,9 @@ def fused_relattn(adt, dk, p_att):
     return FUSED_RELATTN and adt == torch.bfloat16 and dk in (32, 64) and p_att == 0.0
 
 
-BATCH_POS_PROJ = os.environ.get("LASR_BATCH_POS_PROJ", "1") != "0"
+BATCH_POS_PROJ = True
 # a layer's final norm and the next layer's first norm in one launch (lasr_layernorm2_fwd)
-FUSED_LN2 = os.environ.get("LASR_FUSED_LN2", "1") != "0"
+FUSED_LN2 = True
 
 
 def pos_projections(pos, Ws):
@@ -371,8 +399,8 @@ def relmha_backward(gb, ln, pos, sv, w, g, env, p_att, s_att, lnb=None):
 # position kernels without the positional term, Tq queries x Tk keys): scores / softmax /
 # P.V (3 launches forward, 5 backward) become 1 + 2 launches, for the self attention (causal +
 # padding mask) and the source attention over the encoder output (key padding).
-# LASR_FUSED_DEC_ATTN=0 keeps the materialised path.
-FUSED_DEC_ATTN = os.environ.get("LASR_FUSED_DEC_ATTN", "1") != "0"
+# False keeps the materialised path (tests/test_kernels_gpu.py compares the two).
+FUSED_DEC_ATTN = True
 # the decoder FFN branch gradients written by the LayerNorm backward that produces each layer's
 # output gradient (False: a branch_grad launch per layer; the test pins the two bit for bit)
 DEC_GB_IN_LN = True
@@ -655,6 +683,7 @@ class EmbedOutFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dx0):
         sv, mod, env = ctx.sv, ctx.mod, ctx.env
+        LayerLink.leftover(env.links)  # the first node below the stack: every hand-off was collected
         B, T2, F2, C = sv.dims
         w, g = mod.weights(), mod.grads()
         adt, dev = env.adt, dx0.device
@@ -729,71 +758,59 @@ class ConformerLayerFn(torch.autograd.Function):
         pat = env.p_att if tr else 0.0
         adt = env.adt
         x0 = x0.contiguous()
-        # (a) macaron FFN, scale 0.5
-        pre = getattr(env, "pre_ln", None)  # this layer's first norm, computed by the previous layer
-        prev = None  # the previous layer's final norm, when its forward chained into ours
-        if pre is not None and pre[0] == id(layer) and pre[1] == x0.data_ptr():
-            ln_a, ma, ra, prev = pre[2:]
-            env.pre_ln = None
+        link = _link(env, layer)
+        # (a) macaron FFN, scale 0.5; its norm may have come with the previous layer's final one
+        # (prev: that norm's (x4, mf, rf), for the chained backward)
+        pre = link.take_first_norm(x0) if link is not None else None
+        if pre is not None:
+            ln_a, ma, ra, prev = pre
         else:
-            ln_a, _, ma, ra = ln_forward(x0, w.ln_a.g, w.ln_a.b, adt)
+            (ln_a, ma, ra), prev = norm_of(x0, w.ln_a, adt), None
         # every residual projection runs the following norm in its epilogue when the row
-        # kernel takes the shape (res_proj); ln_forward covers the rest
-        pb_ = PostLN(g=w.ln_b.g, b=w.ln_b.b, f32=False, nxt=None)
+        # kernel takes the shape (res_proj); norm_of covers the rest
+        pb_ = PostLN(w.ln_b)
         x1, za, ha = ffn_forward(ln_a, w.ffm.W1, w.ffm.b1, w.ffm.W2, w.ffm.b2, w.act, pff,
                                  _seed(s, 1), x0, 0.5, pd, _seed(s, 2), post=pb_)
         # (b) relative-position MHSA
-        if pb_.y1 is not None:
-            ln_b, mb, rb = pb_.y1, pb_.m1, pb_.r1
-        else:
-            ln_b, _, mb, rb = ln_forward(x1, w.ln_b.g, w.ln_b.b, adt)
-        pp = getattr(env, "pos_proj", None)
-        pc_ = PostLN(g=w.ln_c.g, b=w.ln_c.b, f32=False, nxt=None)
+        ln_b, mb, rb = norm_of(x1, w.ln_b, adt, pb_)
+        pc_ = PostLN(w.ln_c)
         x2, svb = enc_attn_forward(ln_b, pos, w.att, env, x1, pat, _seed(s, 3), pd, _seed(s, 4),
-                                   p=pp.get(id(layer)) if pp else None, post=pc_)
+                                   p=link.pos_p if link is not None else None, post=pc_)
         # (c) convolution module
-        if pc_.y1 is not None:
-            ln_c, mc, rc = pc_.y1, pc_.m1, pc_.r1
-        else:
-            ln_c, _, mc, rc = ln_forward(x2, w.ln_c.g, w.ln_c.b, adt)
-        pd_ = PostLN(g=w.ln_d.g, b=w.ln_d.b, f32=False, nxt=None)
+        ln_c, mc, rc = norm_of(x2, w.ln_c, adt, pc_)
+        pd_ = PostLN(w.ln_d)
         x3, svc = conv_forward(ln_c, w.conv, env, x2, pd, _seed(s, 5), tr, post=pd_)
         # (d) FFN, scale 0.5
-        if pd_.y1 is not None:
-            ln_d, md, rd = pd_.y1, pd_.m1, pd_.r1
-        else:
-            ln_d, _, md, rd = ln_forward(x3, w.ln_d.g, w.ln_d.b, adt)
-        # final LN -> next layer's residual stream (fp32); with the next layer's first norm
-        # chained when the encoder loop names it (env.next_ln): in fc2's epilogue, or in one
-        # lasr_layernorm2_fwd launch
-        nxt = getattr(env, "next_ln", None)
-        chain = FUSED_LN2 and nxt is not None and adt == torch.bfloat16
-        pf_ = PostLN(g=w.ln_f.g, b=w.ln_f.b, f32=True, nxt=(nxt[1], nxt[2]) if chain else None)
+        ln_d, md, rd = norm_of(x3, w.ln_d, adt, pd_)
+        # final LN -> next layer's residual stream (fp32); with the first norm of the layer above
+        # chained (FUSED_LN2): in fc2's epilogue, or in one lasr_layernorm2_fwd launch
+        up = link.above if link is not None and FUSED_LN2 and adt == torch.bfloat16 else None
+        wn = up.layer.weights().ln_a if up is not None else None
+        pf_ = PostLN(w.ln_f, f32=True, nxt=(wn.g, wn.b) if up is not None else None)
         x4, zd, hd = ffn_forward(ln_d, w.ff.W1, w.ff.b1, w.ff.W2, w.ff.b2, w.act, pff,
                                  _seed(s, 6), x3, 0.5, pd, _seed(s, 7), post=pf_)
         if pf_.y1 is not None:
             x5, mf, rf = pf_.y1, pf_.m1, pf_.r1
-            if chain:
-                env.pre_ln = (id(nxt[0]), x5.data_ptr(), pf_.y2, pf_.m2, pf_.r2,
-                              SimpleNamespace(layer=layer, x4=x4, mf=mf, rf=rf))
+            z, m2, r2 = pf_.y2, pf_.m2, pf_.r2
         else:
             x5 = _e(x4.shape, F32, x4.device)
             mf = _e(x4.shape[0], F32, x4.device)
             rf = _e(x4.shape[0], F32, x4.device)
-            if chain:
+            if up is not None:
                 z = _e(x4.shape, adt, x4.device)
                 m2 = _e(x4.shape[0], F32, x4.device)
                 r2 = _e(x4.shape[0], F32, x4.device)
-                K.layernorm2_fwd(x4, w.ln_f.g, w.ln_f.b, nxt[1], nxt[2], LN_EPS, x5, mf, rf, z, m2, r2)
-                env.pre_ln = (id(nxt[0]), x5.data_ptr(), z, m2, r2, SimpleNamespace(layer=layer, x4=x4, mf=mf, rf=rf))
+                K.layernorm2_fwd(x4, w.ln_f.g, w.ln_f.b, wn.g, wn.b, LN_EPS, x5, mf, rf, z, m2, r2)
             else:
                 K.layernorm_fwd(x4, w.ln_f.g, w.ln_f.b, LN_EPS, x5, mf, rf)
+        if up is not None:
+            up.give_first_norm(x5, z, m2, r2, x4, mf, rf)
         if torch.is_grad_enabled() or anchor.requires_grad:
             ctx.sv = SimpleNamespace(x=(x0, x1, x2, x3, x4), ln=(ln_a, ln_b, ln_c, ln_d),
                                      st=((ma, ra), (mb, rb), (mc, rc), (md, rd), (mf, rf)),
                                      za=za, ha=ha, zd=zd, hd=hd, svb=svb, svc=svc, pos=pos,
                                      p=(pd, pff, pat), prev=prev)
-        ctx.layer, ctx.env = layer, env
+        ctx.layer, ctx.env, ctx.link = layer, env, link
         return x5
 
     @staticmethod
@@ -807,21 +824,16 @@ class ConformerLayerFn(torch.autograd.Function):
         (ma, ra), (mb, rb), (mc, rc), (md, rd), (mf, rf) = sv.st
         dev, adt = dx5.device, env.adt
         M, d = x4.shape
-        dx5 = dx5.contiguous()
         # parameter-gradient reductions of the whole layer finish in one launch at the end (or,
         # held, with the layers below it in the same backward segment)
-        rx = getattr(env, "bwd_chain", None)
-        with K.deferred_reductions(hold=_red_hold(env, layer), on_done=layer.on_grads_ready):
-            if rx is not None and rx[0] == id(layer):
-                # the next layer ran this final norm's backward with its own first norm's
-                # (LN2_BWD_CHAIN): dx5 is already dx4, and gb came with it
-                # (this layer's output has one consumer, the next layer -- directly or through a
-                # backward-segment cut, which may hand over a copy -- so dx5 holds exactly the
-                # dx4 values that layer produced)
-                env.bwd_chain = None
-                if rx[1] != (tuple(dx5.shape), dx5.dtype):
-                    raise RuntimeError("ConformerLayerFn: the chained final-norm gradient did not arrive as produced")
-                dx4, gb = dx5, rx[2]
+        link = ctx.link
+        with K.deferred_reductions(hold=_hold(link), on_done=layer.on_grads_ready):
+            # the layer above may have run this final norm's backward with its own first norm's
+            # (LN2_BWD_CHAIN): dx5 is then the very dx4 tensor it produced, and gb came with it
+            gb = link.take_final_grad(dx5) if link is not None else None
+            dx5 = dx5.contiguous()
+            if gb is not None:
+                dx4 = dx5
             else:
                 # final LN; emits the (d)-branch gradient 0.5*drop(dx4)
                 dx4 = _e((M, d), F32, dev)
@@ -852,16 +864,18 @@ class ConformerLayerFn(torch.autograd.Function):
                           dres=dx1, gb=None, bscale=1.0, bp=0.0, bseed=0)
             pv = sv.prev if LN2_BWD_CHAIN else None
             if pv is not None:
-                # the previous layer's final norm on dx0 in the same launch: it receives dx4 / gb
-                pw, pgr = pv.layer.weights(), pv.layer.grads()
+                # the layer below's final norm on dx0 in the same launch: it receives dx4 / gb
+                below = link.below.layer
+                pw, pgr = below.weights(), below.grads()
                 dx4p, gbp = _e((M, d), F32, dev), _e((M, d), adt, dev)
-                lnb_a.chain = LnBwd(x=pv.x4, g=pw.ln_f.g, mean=pv.mf, rstd=pv.rf, dx=dx4p, dgamma=pgr.ln_f.g,
+                lnb_a.chain = LnBwd(x=pv[0], g=pw.ln_f.g, mean=pv[1], rstd=pv[2], dx=dx4p, dgamma=pgr.ln_f.g,
                                     dbeta=pgr.ln_f.b, dres=None, gb=gbp, bscale=0.5, bp=pd,
-                                    bseed=_seed(pv.layer.seed, 7))
+                                    bseed=_seed(below.seed, 7))
             ffn_backward(gb1, ln_a, sv.za, sv.ha, w.ffm.W1, w.ffm.W2, g.ffm.W1, g.ffm.b1, g.ffm.W2, g.ffm.b2,
                          w.act, pff, _seed(s, 1), lnb=lnb_a)
             if pv is not None:
-                env.bwd_chain = (id(pv.layer), (tuple(dx4p.shape), dx4p.dtype), gbp)
+                # autograd carries dx4p to that layer's node in place of this layer's input gradient
+                link.below.give_final_grad(dx4p, gbp)
                 dx0 = dx4p
         ctx.sv = None
         return dx0, None, None, None, None
@@ -884,21 +898,18 @@ class TransformerLayerFn(torch.autograd.Function):
         pat = env.p_att if tr else 0.0
         adt = env.adt
         x0 = x0.contiguous()
-        ln_b, _, mb, rb = ln_forward(x0, w.ln_b.g, w.ln_b.b, adt)
-        pp = getattr(env, "pos_proj", None)
-        pd_ = PostLN(g=w.ln_d.g, b=w.ln_d.b, f32=False, nxt=None)
+        link = _link(env, layer)
+        ln_b, mb, rb = norm_of(x0, w.ln_b, adt)
+        pd_ = PostLN(w.ln_d)
         x1, svb = enc_attn_forward(ln_b, pos, w.att, env, x0, pat, _seed(s, 3), pd, _seed(s, 4),
-                                   p=pp.get(id(layer)) if pp else None, post=pd_)
-        if pd_.y1 is not None:
-            ln_d, md, rd = pd_.y1, pd_.m1, pd_.r1
-        else:
-            ln_d, _, md, rd = ln_forward(x1, w.ln_d.g, w.ln_d.b, adt)
+                                   p=link.pos_p if link is not None else None, post=pd_)
+        ln_d, md, rd = norm_of(x1, w.ln_d, adt, pd_)
         x2, zd, hd = ffn_forward(ln_d, w.ff.W1, w.ff.b1, w.ff.W2, w.ff.b2, w.act, pff, _seed(s, 6), x1, 1.0, pd,
                                  _seed(s, 7))
         if torch.is_grad_enabled() or anchor.requires_grad:
             ctx.sv = SimpleNamespace(x=(x0, x1), ln=(ln_b, ln_d), st=((mb, rb), (md, rd)), zd=zd, hd=hd, svb=svb,
                                      pos=pos, p=(pd, pff, pat))
-        ctx.layer, ctx.env = layer, env
+        ctx.layer, ctx.env, ctx.link = layer, env, link
         return x2
 
     @staticmethod
@@ -913,7 +924,7 @@ class TransformerLayerFn(torch.autograd.Function):
         dev, adt = dx2.device, env.adt
         M, d = x1.shape
         dx2 = dx2.contiguous()
-        with K.deferred_reductions(hold=_red_hold(env, layer), on_done=layer.on_grads_ready):
+        with K.deferred_reductions(hold=_hold(ctx.link), on_done=layer.on_grads_ready):
             gb = _e((M, d), adt, dev)
             K.branch_grad(dx2, gb, 1.0, pd, _seed(s, 7))
             dx1 = _e((M, d), F32, dev)
@@ -953,42 +964,30 @@ def decoder_layers_fwd(dec, wd, y, h, B, L1, T, masks, p, adt, seed_shift=0):
     kvm = _e((B * T, len(wd.layers) * 2 * wd.d), adt, y.device)
     K.linear(h, wd.kv_all.W, kvm, bias=wd.kv_all.b)
     def post_ln(ln):  # the norm after a residual projection, in its launch (res_proj)
-        return PostLN(g=ln.g, b=ln.b, f32=False, nxt=None) if DEC_ROW_LN else None
-
-    def ln_after(x, post, ln):  # post's outputs, or the norm as its own launch
-        if post is not None and post.y1 is not None:
-            return post.y1, post.m1, post.r1
-        l_, _, m_, r_ = ln_forward(x, ln.g, ln.b, adt)
-        return l_, m_, r_
+        return PostLN(ln) if DEC_ROW_LN else None
 
     nxt = None  # (l1, m1, r1) of the next layer, formed in this layer's fc2 launch
     for i, lw in enumerate(wd.layers):
         s = dec.dec_layers[i].seed + seed_shift
-        if nxt is None:
-            l1, _, m1, r1 = ln_forward(y, lw.ln1.g, lw.ln1.b, adt)
-        else:
-            l1, m1, r1 = nxt
+        l1, m1, r1 = nxt if nxt is not None else norm_of(y, lw.ln1, adt)
         p2 = post_ln(lw.ln2)
         y1, sa = mha_forward(l1, None, lw.sa, B, L1, L1, wd.H, smask, smsb, smsq, y, pat, _seed(s, 1), pd,
                              _seed(s, 2), post=p2)
-        l2, m2, r2 = ln_after(y1, p2, lw.ln2)
+        l2, m2, r2 = norm_of(y1, lw.ln2, adt, p2)
         p3 = post_ln(lw.ln3)
         y2, ca = mha_forward(l2, h, lw.ca, B, L1, T, wd.H, mmask, T, 0, y1, pca, _seed(s, 3), pd, _seed(s, 4),
                              kv=kvm[:, 2 * wd.d * i: 2 * wd.d * (i + 1)], post=p3)
-        l3, m3, r3 = ln_after(y2, p3, lw.ln3)
+        l3, m3, r3 = norm_of(y2, lw.ln3, adt, p3)
         # the next norm (the next layer's first, or after_norm) after the FFN's residual add
         ln_n = wd.layers[i + 1].ln1 if i + 1 < len(wd.layers) else wd.ln_f
-        p4 = PostLN(g=ln_n.g, b=ln_n.b, f32=False, nxt=None)
+        p4 = PostLN(ln_n)
         y3, z, hh = ffn_forward(l3, lw.ff.W1, lw.ff.b1, lw.ff.W2, lw.ff.b2, ACT_RELU, pff, _seed(s, 5), y2, 1.0, pd,
                                 _seed(s, 6), post=p4)
-        nxt = ln_after(y3, p4, ln_n)
+        nxt = norm_of(y3, ln_n, adt, p4)
         layers_sv.append(SimpleNamespace(y=(y, y1, y2), ln=(l1, l2, l3), st=((m1, r1), (m2, r2), (m3, r3)), sa=sa,
                                          ca=ca, z=z, hh=hh))
         y = y3
-    if nxt is None:
-        yf, _, mf, rf = ln_forward(y, wd.ln_f.g, wd.ln_f.b, adt)
-    else:
-        yf, mf, rf = nxt
+    yf, mf, rf = nxt if nxt is not None else norm_of(y, wd.ln_f, adt)
     h_attn = K.padded_rows(R, wd.Wout.shape[0], adt, y.device)
     K.linear(yf, wd.Wout, h_attn, bias=wd.bout)
     return h_attn, SimpleNamespace(layers=layers_sv, yL=y, yf=yf, mf=mf, rf=rf, p=p, masks=masks,

@@ -1,9 +1,12 @@
 """Child process of tests/test_switches_gpu.py: one bf16 training step (forward + hybrid loss +
 backward) of BASELINE config 2's full model (12 / 6 layers, d 256, V 4233) at B 2 x T 1000,
 dropout 0.1, from seeded weights and batch; saves the loss, the flat gradient and the BN
-running statistics.  The environment of the process selects the A/B switch under test (they
-are read once, at import / library load)."""
+running statistics.  The A/B switch under test: a C-side one through the environment of the
+process (read once, at library load), a Python one as a MODULE.ATTR=VALUE argument after the
+output path (tools/flag_ab.py's format), set here before the model is built."""
 
+import ast
+import importlib
 import os
 import sys
 
@@ -13,7 +16,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def main(out_path):
+def main(out_path, sets=()):
+    for item in sets:
+        name, val = item.split("=", 1)
+        mod, attr = name.rsplit(".", 1)
+        m = importlib.import_module(mod)
+        assert hasattr(m, attr), name
+        setattr(m, attr, ast.literal_eval(val))
     from bench import CONFIGS, V, build
     from liteasr_amd.criterions.hybrid_ctc_attn import HybridCTCLoss, HybridCTCLossConfig
     from liteasr_amd.utils.synthetic import synthetic_batch
@@ -34,4 +43,4 @@ def main(out_path):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    main(sys.argv[1], sys.argv[2:])

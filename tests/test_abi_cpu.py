@@ -127,11 +127,12 @@ def test_comm_header_symbols_exported():
 
 def test_switch_names_are_every_product_switch():
     """The getenv switches in csrc/ and the LASR_* environment reads in liteasr_amd/ are exactly
-    the ones tested here (plus LASR_ROCTX, the tracing flag, and the decoder attention switch
-    held to the materialised path in test_kernels_gpu.py)."""
+    the C-side ones tested there (plus LASR_ROCTX, the tracing flag), and every Python switch it
+    names is an attribute of the module it names."""
+    import importlib
     import re
 
-    from test_switches_gpu import SWITCHES
+    from test_switches_gpu import ENV_SWITCHES, PY_MODULE, PY_SWITCHES
 
     found = set()
     for base, _, files in os.walk(os.path.join(ROOT, "liteasr_amd")):
@@ -140,4 +141,8 @@ def test_switch_names_are_every_product_switch():
                 src = open(os.path.join(base, f)).read()
                 found |= set(re.findall(r'getenv\("(LASR_[A-Z0-9_]+)"', src))
                 found |= set(re.findall(r'environ\.get\("(LASR_[A-Z0-9_]+)"', src))
-    assert found == set(SWITCHES) | {"LASR_ROCTX", "LASR_FUSED_DEC_ATTN"}, found
+    assert found == set(ENV_SWITCHES) | {"LASR_ROCTX"}, found
+    assert set(ENV_SWITCHES) == {"LASR_EPI_SPEC", "LASR_DW_SLICE_XCD", "LASR_CTC_REGS"}
+    mod = importlib.import_module(PY_MODULE)
+    for attr in PY_SWITCHES:
+        assert getattr(mod, attr) is True, attr

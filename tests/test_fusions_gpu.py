@@ -19,7 +19,7 @@ from oracle import u2_oracle as O  # noqa: E402
 CFG = O.default_cfg(enc_layers=2, dec_layers=3)  # small-model widths (d 256, ff 2048, V 4233)
 
 
-def _step(cfg, B=3, T=300, L=9, dropout=0.1, seed=4):
+def _model(cfg, dropout=0.1, seed=4):
     from liteasr_amd.criterions.hybrid_ctc_attn import HybridCTCLoss, HybridCTCLossConfig
     from liteasr_amd.models.u2 import U2, U2Config
     from liteasr_amd.utils.cfg import resolve_self
@@ -33,7 +33,11 @@ def _step(cfg, B=3, T=300, L=9, dropout=0.1, seed=4):
     m = U2(c)
     m.load_state_dict({**O.init_params(cfg, seed=seed), **O.init_buffers(cfg)}, strict=False)
     m = m.cuda().train()
-    crit = HybridCTCLoss(HybridCTCLossConfig(vocab_size=cfg["vocab_size"], smoothing=0.1, ctc_weight=0.3))
+    return m, HybridCTCLoss(HybridCTCLossConfig(vocab_size=cfg["vocab_size"], smoothing=0.1, ctc_weight=0.3))
+
+
+def _step(cfg, B=3, T=300, L=9, dropout=0.1, seed=4):
+    m, crit = _model(cfg, dropout, seed)
     xs, xl, ys, yl = [t.cuda() for t in O.synthetic_batch(B, T, L, cfg["vocab_size"], seed=seed)]
     loss = crit(m, xs, xl, ys, yl)
     loss.backward()
@@ -161,3 +165,51 @@ def test_layer_reductions_held_across_layers(monkeypatch, d, heads):
     monkeypatch.setattr(FN, "LAYER_RED_HOLD", False)
     off = _step(cfg, B=4, T=1000, L=12)
     _same(on, off)
+
+
+def test_chained_norm_gradient_crosses_a_cut_only_as_the_tensor_produced():
+    """LN2_BWD_CHAIN across a backward-segment cut: layer 1's node returns layer 0's dx4 (and
+    leaves gb in layer 0's link record), so the gradient taken at the cut is correct for layer 0
+    only as the very tensor that node produced.  2 encoder layers / 1 decoder layer, d 256, B 2,
+    T 100 (T' 24), L 4, bf16, dropout 0.1 (the row kernel and both chains are live):
+    autograd.grad to the cut's leaf + autograd.backward from the cut gives the unsegmented flat
+    gradient bit for bit; handing on a clone of that gradient (same values: what a hook or a
+    second consumer would deliver) raises, leaves no reduction queued, and the next normal step
+    is again bit-identical."""
+    from liteasr_amd import kernels as kn
+
+    cfg = O.default_cfg(enc_layers=2, dec_layers=1)
+    m, crit = _model(cfg)
+    batch = [t.cuda() for t in O.synthetic_batch(2, 100, 4, cfg["vocab_size"], seed=4)]
+
+    def start():  # the same step every time: same dropout draws, gradients from zero
+        m._drop_ctr.zero_()
+        m.store.ensure_grad().zero_()
+
+    def to_cut():
+        start()
+        with m.segmented([1]) as pairs:
+            loss = crit(m, *batch)
+        (_, x, leaf), = pairs
+        (g,) = torch.autograd.grad(loss, [leaf])
+        return x, g
+
+    def whole():
+        start()
+        crit(m, *batch).backward()
+        torch.cuda.synchronize()
+        return m.store.grad.clone()
+
+    ref = whole()
+    assert ref.abs().max().item() > 0
+    x, g = to_cut()
+    torch.autograd.backward(x, g)
+    torch.cuda.synchronize()
+    assert torch.equal(m.store.grad, ref), (m.store.grad - ref).abs().max().item()
+    assert kn.held_reductions() == 0
+
+    x, g = to_cut()
+    with pytest.raises(RuntimeError, match="did not arrive as produced"):
+        torch.autograd.backward(x, g.clone())
+    assert kn.held_reductions() == 0
+    assert torch.equal(whole(), ref)

@@ -1,6 +1,7 @@
-"""Host-side logic that needs no GPU: the attention mask re-layout (kernels._fwd_mask) and the
+"""Host-side logic that needs no GPU: the attention mask re-layout (kernels._fwd_mask), the
 FlatReducer's once-per-run check of the native reducer (ddp.FlatReducer._verify_native),
-driven over gloo world 2 with a stand-in for the C reducer."""
+driven over gloo world 2 with a stand-in for the C reducer, the deferred-reduction queue
+(kernels.deferred_reductions) and the encoder layers' link records (nets/links.py)."""
 
 import os
 import socket
@@ -162,3 +163,101 @@ def test_held_reductions_queue_order(monkeypatch):
             K._defer("E", 1, 4, None)
             raise ValueError
     assert launched[-1] == ["E"] and events[-1] == ("E", 2) and K.held_reductions() == 0
+
+
+def test_nested_deferred_block_refuses_hold_and_on_done(monkeypatch):
+    """A deferred_reductions block inside another one ends without launching or queueing
+    anything, so it cannot honour hold=True or an on_done callback: it raises instead of
+    dropping them (a dropped on_done is a gradient bucket that never fires).  A plain nested
+    block is still fine."""
+    from liteasr_amd import kernels as K
+
+    launched, events = [], []
+    monkeypatch.setattr(K, "_flush_node_end", lambda segs: launched.append([s[0] for s in segs]))
+    monkeypatch.setattr(K, "_DEFER", K._Deferred())
+    with K.deferred_reductions(on_done=lambda: events.append("outer")):
+        K._defer("a", 1, 4, None)
+        with pytest.raises(RuntimeError, match="inside another deferred block"):
+            with K.deferred_reductions(on_done=lambda: events.append("inner")):
+                pass
+        with pytest.raises(RuntimeError, match="inside another deferred block"):
+            with K.deferred_reductions(hold=True):
+                pass
+        with K.deferred_reductions():
+            K._defer("b", 1, 4, None)
+        assert launched == [] and events == []
+    assert launched == [["a", "b"]] and events == ["outer"] and K.held_reductions() == 0
+
+
+class _L:
+    """Stand-in for an encoder layer module (a LayerLink only keeps and hashes it)."""
+
+
+def test_layer_link_floor_follows_the_segment_cuts():
+    """floor marks the lowest layer of each backward segment: layer 0, and layer j for every
+    cut before a layer j of the stack (-1, inside the subsampling, and 4, above the last of 4
+    layers, are cuts elsewhere in the model); neighbours are linked bottom up."""
+    from liteasr_amd.nets.links import LayerLink
+
+    layers = [_L() for _ in range(4)]
+    floors = lambda links: {j for j, l in enumerate(layers) if links[l].floor}  # noqa: E731
+    assert floors(LayerLink.stack(layers)) == {0}
+    links = LayerLink.stack(layers, cuts=frozenset({-1, 1, 3, 4}), pos_p=["p0", "p1", "p2", "p3"])
+    assert floors(links) == {0, 1, 3}
+    assert [links[l].pos_p for l in layers] == ["p0", "p1", "p2", "p3"]
+    assert LayerLink.stack(layers)[layers[2]].pos_p is None
+    for j, l in enumerate(layers):
+        assert links[l].layer is l
+        assert links[l].below is (links[layers[j - 1]] if j else None)
+        assert links[l].above is (links[layers[j + 1]] if j < 3 else None)
+    with pytest.raises(AttributeError):
+        links[layers[0]].flor = True  # declared fields only
+
+
+def test_layer_link_forward_handoff_matches_storage():
+    """The first norm the layer below computed is taken only by an x0 that is the storage it was
+    computed from (a detached view of it included: a segment cut's leaf), and only once."""
+    from liteasr_amd.nets.links import LayerLink
+
+    low, top = LayerLink.stack([_L(), _L()]).values()
+    x5, other = torch.zeros(6, 4), torch.zeros(6, 4)
+    z, m, r, x4, mf, rf = (torch.full((1,), float(i)) for i in range(6))
+    assert top.take_first_norm(x5) is None  # nothing deposited
+    top.give_first_norm(x5, z, m, r, x4, mf, rf)
+    assert top.take_first_norm(other) is None and top.take_first_norm(x5.clone()) is None
+    got = top.take_first_norm(x5.detach())
+    assert got[0] is z and got[1] is m and got[2] is r
+    assert got[3][0] is x4 and got[3][1] is mf and got[3][2] is rf
+    assert top.take_first_norm(x5) is None  # taking cleared it
+    assert low.take_first_norm(x5) is None  # (it was the top layer's)
+
+
+def test_layer_link_backward_handoff_is_identity_checked():
+    """The dx4 a layer returned for the layer below is accepted there only as the very tensor:
+    a clone (same values), another shape or another dtype raises; it is taken once; an
+    uncollected one is found by the check the first node below the stack runs."""
+    from liteasr_amd.nets.links import LayerLink
+
+    def fresh():
+        links = LayerLink.stack([_L(), _L()])
+        low, top = links.values()
+        return links, low, torch.ones(6, 4), torch.ones(6, 4, dtype=torch.bfloat16)
+
+    links, low, dx4, gb = fresh()
+    assert low.take_final_grad(dx4) is None  # no deposit: the layer runs its own final norm
+    LayerLink.leftover(links)
+    LayerLink.leftover(None)  # a standalone node's env
+    low.give_final_grad(dx4, gb)
+    with pytest.raises(RuntimeError, match="never collected"):
+        LayerLink.leftover(links)
+    assert low.take_final_grad(dx4) is gb
+    assert low.take_final_grad(dx4) is None
+    LayerLink.leftover(links)
+    # a copy; another shape / dtype, both as new tensors and as views of the same storage
+    for wrong in (torch.clone, lambda t: torch.ones(4, 6), lambda t: t.double(), lambda t: t.view(3, 8),
+                  lambda t: t.view(torch.int32)):
+        links, low, dx4, gb = fresh()
+        low.give_final_grad(dx4, gb)
+        with pytest.raises(RuntimeError, match="did not arrive as produced"):
+            low.take_final_grad(wrong(dx4))
+        LayerLink.leftover(links)  # a refused hand-over is cleared too

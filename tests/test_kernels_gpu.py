@@ -400,7 +400,7 @@ def test_attn_key_split(B, H, Tq, Tk, dk, qmask, splits):
 @pytest.mark.parametrize("kind", ["self-masked", "self-nomask", "source"])
 def test_decoder_attention_fused_matches_materialised(kind, monkeypatch):
     """Decoder attention on the fused kernels without the positional term (lasr_attn_fwd /
-    lasr_attn_bwd through functional.mha_forward / mha_backward, LASR_FUSED_DEC_ATTN)
+    lasr_attn_bwd through functional.mha_forward / mha_backward, FUSED_DEC_ATTN)
     against the materialised-score path on the same inputs: self attention with the causal +
     key-padding mask (U2) or none (Paraformer's parallel decoder), and source attention over
     an encoder output (Tq 41 != Tk 249, key padding); B 32, d 256, 4 heads, bf16."""

@@ -64,7 +64,7 @@ def _env(model, seed, shape=(B, TX, L)):
     xs = xs.bfloat16().float()
     with torch.no_grad():
         _, prep, env = model._run_encoder(xs.cuda(), xlens.cuda(), ys.cuda(), ylens.cuda())
-    env.next_ln = env.pre_ln = env.pos_proj = None
+    env.links = None
     return env, prep, (xs, xlens, ys, ylens)
 
 

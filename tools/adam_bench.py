@@ -1,6 +1,7 @@
 """Times lasr_adam_step (the finalize launch + the Adam launch) over flat buffers of the small
 config's parameter count and prints a hash of the updated parameters, momenta and bf16 copy
-after a fixed number of steps, so that library builds (LITEASR_HIP_LIB) compare bit for bit."""
+after a fixed number of steps, so that library builds compare bit for bit
+(another build: python tools/with_lib.py LIB tools/adam_bench.py [n])."""
 import hashlib
 import json
 import os

@@ -1,6 +1,6 @@
 """Bitwise A/B of the fused attention kernels between two builds of libliteasr_hip.so.
 
-    LITEASR_HIP_LIB=<lib> python tools/attn_check.py dump OUT.pt   # every output of every case
+    python tools/with_lib.py LIB tools/attn_check.py dump OUT.pt   # every output of every case
     python tools/attn_check.py cmp A.pt B.pt                         # JSON line per tensor
 
 Cases are attn_bench.py's shapes (relative-position self attention of configs 2 / 4 / 5, the

@@ -1,7 +1,8 @@
 """Times lasr_conv1_fwd / lasr_conv1_bwd (subsampling conv1, 1 -> C channels, 3x3 stride 2, bf16
 channels-last y1) and prints a hash of the forward output, so that library builds
-(LITEASR_HIP_LIB) compare bit for bit.  HBM bytes: y1 written (fwd) / dy1 read (bwd).
-Usage: python tools/conv1_bench.py [B T F C]   (default: the small and large configs, C 256 / 512)"""
+compare bit for bit.  HBM bytes: y1 written (fwd) / dy1 read (bwd).
+Usage: python tools/conv1_bench.py [B T F C]   (default: the small and large configs, C 256 / 512);
+another build of the library: python tools/with_lib.py LIB tools/conv1_bench.py [B T F C]"""
 import hashlib
 import json
 import os

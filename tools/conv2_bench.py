@@ -1,7 +1,8 @@
 """Time lasr_conv2_gemm (fwd / dW / dX) at a config's subsampling size and print hashes of
-the outputs, so two processes (e.g. two library builds via LITEASR_HIP_LIB) can be compared bit for
+the outputs, so two processes (e.g. two library builds) can be compared bit for
 bit (forward and data gradient: same k order per output, so equal hashes are expected).
-Usage: python tools/conv2_bench.py [B T F C]"""
+Usage: python tools/conv2_bench.py [B T F C]; another build of the library:
+python tools/with_lib.py LIB tools/conv2_bench.py [B T F C]"""
 import hashlib
 import json
 import os

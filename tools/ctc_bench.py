@@ -1,7 +1,8 @@
 """Times the three CTC kernels (row lse + gather, alpha/beta lattice, gradient) at the small
 and long configs through bench.ctc_roofline; one JSON line per config, with a hash of the
 kernels' outputs on the same inputs so that library builds compare bit for bit.
-LITEASR_HIP_LIB selects the library (ablation builds from tools/gemm_exp.sh, EXP_FILES=ctc)."""
+python tools/with_lib.py LIB tools/ctc_bench.py runs another build of the library (ablation
+builds from tools/gemm_exp.sh, EXP_FILES=ctc)."""
 import hashlib
 import json
 import os

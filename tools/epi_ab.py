@@ -1,8 +1,8 @@
 """FFN fc1 GEMM epilogue timings at config 2's shape (M 7968, N 2048, K 256), each a replayed
 hipGraph of 50 launches timed with HIP events: the forward (bias + Swish + stored gate +
 dropout, zout_mode 1), the backward dz (x stored gate, dropout scale), and the plain GEMM of the
-same shape.  Run once per library (LITEASR_HIP_LIB: e.g. the LASR_EXP ablation builds of
-tools/gemm_exp.sh) -> one JSON line per case."""
+same shape.  Run once per library (python tools/with_lib.py LIB tools/epi_ab.py: e.g. the LASR_EXP
+ablation builds of tools/gemm_exp.sh) -> one JSON line per case."""
 
 import hashlib
 import json
