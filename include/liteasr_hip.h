@@ -461,6 +461,23 @@ typedef struct lasr_cif_args {
 } lasr_cif_args;
 int lasr_cif_fwd(const lasr_cif_args* args, void* stream);
 int lasr_cif_bwd(const lasr_cif_args* args, void* stream);
+/* Inference-mode integrate-and-fire (liteasr/nets/paraformer/predictor.py:41-53 with
+ * ylens = None, then :56-118): the token count is a device result.  alpha and sum_alpha as
+ * in lasr_cif_fwd (same summation order); ulen[b] = (int)rintf(sum_alpha[b]) (half to even,
+ * torch.round); beta = sum_alpha / ulen - 1e-4; the same fire rule and the same "a fired
+ * state that is exactly zero does not count" rule.  out is [B, T, D] (at most T states can
+ * fire): row u < count[b] of utterance b is its u-th counted fired state, bit-identical to
+ * lasr_cif_fwd's with ylen = ulen; every later row is zero.  ulen = 0: beta = +inf, nothing
+ * fires, all rows zero.  alpha, acc, fired, row [B*T] in lasr_cif_fwd's layouts; count[b] =
+ * counted fired states.  Three launches (scalar recursion per utterance; one wave per fired
+ * frame; compaction over zero states), no host round trip, no allocation, no atomics.
+ * D in {64, 128, 256, 512}; any other D returns LASR_ERR_INVALID. */
+typedef struct lasr_cif_infer_args {
+  int B, T, D;
+  const float* z; const int* plen; const float* h;
+  float* alpha; float* acc; uint8_t* fired; int* row; float* sum_alpha; int* ulen; int* count; float* out;
+} lasr_cif_infer_args;
+int lasr_cif_infer(const lasr_cif_infer_args* args, void* stream);
 /* Glancing sampler mix (liteasr/nets/paraformer/glancing_sampler.py:32), fp32 [rows, D],
  * replace u8 [rows]: fwd out = replace ? a : b; bwd (a = the incoming gradient)
  * out = replace ? a : 0 (embedding branch), out2 = replace ? 0 : a (CIF branch). */

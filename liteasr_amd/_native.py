@@ -77,6 +77,17 @@ class CifArgs(C.Structure):
     ]
 
 
+class CifInferArgs(C.Structure):
+    """Mirror of ``lasr_cif_infer_args``."""
+
+    _fields_ = [
+        ("B", _i), ("T", _i), ("D", _i),
+        ("z", _p), ("plen", _p), ("h", _p),
+        ("alpha", _p), ("acc", _p), ("fired", _p), ("row", _p), ("sum_alpha", _p), ("ulen", _p), ("count", _p),
+        ("out", _p),
+    ]
+
+
 class RowLnArgs(C.Structure):
     """Mirror of ``lasr_row_ln_args``."""
 
@@ -177,6 +188,7 @@ SIGNATURES = {
     "lasr_conv2_dx_w1_workspace": [_i, _i, _i, _i],
     "lasr_cif_fwd": [C.POINTER(CifArgs), _p],
     "lasr_cif_bwd": [C.POINTER(CifArgs), _p],
+    "lasr_cif_infer": [C.POINTER(CifInferArgs), _p],
     "lasr_glancing_mix": [_l, _i, _p, _p, _p, _p, _p, _i, _p],
     "lasr_im2col3x3s2": [_p, _i, _i, _i, _i, _i, _p, _p],
     "lasr_col2im3x3s2": [_p, _i, _i, _i, _i, _i, _p, _p, _p],

@@ -65,8 +65,10 @@ def _mem_mask(B, T, dev):
     return torch.zeros(B, T, dtype=torch.uint8, device=dev)
 
 
-def encode(model, x, graph=True):
+def encode(model, x, graph=True, fp32=False):
     """`self.encoder(x)` for one utterance x [1, T, F] (no padding mask) -> (h [T', d], T').
+    h is in the compute dtype; with ``fp32`` it is the fp32 after_norm output (what the
+    Paraformer predictor integrates).
 
     With ``graph`` the ~250 encoder launches of a batch-1 utterance (launch-latency-bound)
     are captured once per input shape into a hipGraph and replayed; the returned h is that
@@ -79,11 +81,11 @@ def encode(model, x, graph=True):
     if x.device.type != "cuda":
         raise RuntimeError("liteasr_amd decoding runs on the HIP device only")
     if not graph:
-        return _encode_eager(model, x)
+        return _encode_eager(model, x, fp32)
     st = model.store
     # model.training too: dropout and BatchNorm (batch vs running statistics) are baked
     # into the captured launches, so a train()/eval() switch must re-capture
-    key = (tuple(x.shape), x.dtype, st.flat._version, st.generation, bool(model.training))
+    key = (tuple(x.shape), x.dtype, st.flat._version, st.generation, bool(model.training), bool(fp32))
     cache = model.__dict__.setdefault("_encode_graphs", {})
     e = cache.get(key)
     if e is None:
@@ -93,12 +95,12 @@ def encode(model, x, graph=True):
         side = torch.cuda.Stream()
         side.wait_stream(cur)
         with torch.cuda.stream(side):  # warm-up: workspaces, working copies, allocator pools
-            _encode_eager(model, static)
+            _encode_eager(model, static, fp32)
         cur.wait_stream(side)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            h, T = _encode_eager(model, static)
+            h, T = _encode_eager(model, static, fp32)
         # keep the workspace the graph was captured against alive even if it is regrown
         e = cache[key] = (g, static, h, T, K.WS.buf.get(x.device.index))
     g, static, h, T, _ = e
@@ -107,13 +109,13 @@ def encode(model, x, graph=True):
     return h, T
 
 
-def _encode_eager(model, x):
+def _encode_eager(model, x, fp32=False):
     B, Tx = x.shape[0], x.shape[1]
     xlens = torch.full((B,), Tx, dtype=torch.int64, device=x.device)
     ys = torch.full((B, 1), -1, dtype=torch.int64, device=x.device)
     ylens = torch.zeros(B, dtype=torch.int64, device=x.device)
     xe, prep, _ = model._run_encoder(x, xlens, ys, ylens)
-    return FN.encoder_out(xe, model, model.compute_dtype), prep.T
+    return FN.encoder_out(xe, model, torch.float32 if fp32 else model.compute_dtype), prep.T
 
 
 def ctc_prefix_beam_search_nbest(model, x, beam=10):

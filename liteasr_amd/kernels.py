@@ -12,6 +12,7 @@ import contextlib
 import os
 import ctypes as C
 import math
+from types import SimpleNamespace
 from typing import Optional
 
 import torch
@@ -1089,6 +1090,31 @@ def cif_bwd(plen, ylen, h, B, T, U, st, gout, gsum, dz, dh):
         ptr(st.sum_alpha)
     a.gout, a.gsum, a.dz, a.dh = ptr(gout), ptr(gsum), ptr(dz), ptr(dh)
     N.call("lasr_cif_bwd", C.byref(a), stream())
+
+
+def cif_infer(z, plen, h, st=None):
+    """Inference-mode integrate-and-fire (lasr_cif_infer): z fp32 [B*T'] (any shape with B*T'
+    elements), plen int32 [B], h fp32 [B, T', D] -> SimpleNamespace(alpha, acc, fired, row
+    [B*T'], sum_alpha [B], ulen, count int32 [B], out [B, T', D] fp32), all on the device.
+    st: a namespace of those buffers to write into (graph replays); allocated when None."""
+    B, T, D = h.shape
+    dev = h.device
+    if z.dtype != torch.float32 or h.dtype != torch.float32 or plen.dtype != torch.int32:
+        raise ValueError("cif_infer: z / h fp32 and plen int32")
+    if z.numel() != B * T or plen.numel() != B or not (z.is_contiguous() and h.is_contiguous()):
+        raise ValueError("cif_infer: z [B*T'], plen [B], h [B, T', D] contiguous")
+    if st is None:
+        e = lambda n, dt: torch.empty(n, dtype=dt, device=dev)  # noqa: E731
+        st = SimpleNamespace(alpha=e(B * T, torch.float32), acc=e(B * T, torch.float32), fired=e(B * T, torch.uint8),
+                             row=e(B * T, torch.int32), sum_alpha=e(B, torch.float32), ulen=e(B, torch.int32),
+                             count=e(B, torch.int32), out=e((B, T, D), torch.float32))
+    a = N.CifInferArgs()
+    a.B, a.T, a.D = B, T, D
+    a.z, a.plen, a.h = ptr(z), ptr(plen), ptr(h)
+    a.alpha, a.acc, a.fired, a.row = ptr(st.alpha), ptr(st.acc), ptr(st.fired), ptr(st.row)
+    a.sum_alpha, a.ulen, a.count, a.out = ptr(st.sum_alpha), ptr(st.ulen), ptr(st.count), ptr(st.out)
+    N.call("lasr_cif_infer", C.byref(a), stream())
+    return st
 
 
 def glancing_mix(replace, a, b, out, out2=None, backward=False):

@@ -18,7 +18,8 @@ from __future__ import annotations
 
 import random
 from dataclasses import dataclass, field
-from typing import Optional
+from types import SimpleNamespace
+from typing import List, Optional
 
 import torch
 import torch.nn as nn
@@ -28,7 +29,12 @@ from ..config import II, MISSING, LiteasrDataclass
 from ..nets import functional as FN
 from ..nets.modules import ParallelDecoder, PositionalEncoding, Predictor, TransformerEncoder
 from . import register_model
-from ._fused import FusedEncoderModel
+from ._fused import FusedEncoderModel, _require_hip
+
+
+def _sub_len(T):
+    """Frames after the Conv2d subsampling (paraformer.py:131-133)."""
+    return ((T - 1) // 2 - 1) // 2
 
 
 @dataclass
@@ -114,6 +120,45 @@ class Paraformer(FusedEncoderModel):
                                                         ylens_host, self.rng)
         self.last_count = int(ylens_host.sum())
         return hs_attn.view(prep.B, ys.shape[1], -1), sum_alpha
+
+    # ------------------------------------------------------------------ decoding
+    @torch.no_grad()
+    def inference_batch(self, xs, xlens) -> List[List[int]]:
+        """The reference's modules composed as ``forward`` composes them, the predictor in its
+        inference branch: encoder(xs, padding_mask(xlens)) -> predictor(h, get_pred_len(xlens),
+        None) -> decoder(h_cif, memory=h, memory_mask) -> argmax; row b trimmed to its first
+        ulen_b ids.  Call it on a model in eval mode (the encoder follows ``self.training``,
+        as in the reference); the decoder pass runs with every dropout rate 0."""
+        _require_hip(self, xs)
+        if _sub_len(xs.shape[1]) < 1:
+            raise ValueError(f"Paraformer.inference: {xs.shape[1]} frames subsample to none (Conv2d needs T >= 7)")
+        xl = torch.as_tensor(xlens, dtype=torch.int64).to(xs.device)
+        h, _ = self.encode(xs, xl)
+        prep = self.last_prep
+        B, T = prep.B, prep.T
+        cif, ulens, ids, logits = FN.paraformer_decode(self, h.reshape(B * T, -1), prep.pred_len, prep.enc_mask, B, T)
+        self.last_decode = SimpleNamespace(cif=cif, ulens=ulens, logits=logits, h=h)
+        return [[] if ids is None else ids[b, :u].tolist() for b, u in enumerate(ulens)]
+
+    @torch.no_grad()
+    def inference(self, x) -> List[int]:
+        """paraformer.py:124-129 for one utterance x [1, T, F]: the token ids.  The same
+        computation as ``inference_batch(x, [T])[0]`` (nothing is padded), with the encoder's
+        launches replayed from its per-shape hipGraph (decoding.encode)."""
+        from .. import decoding
+
+        _require_hip(self, x)
+        if x.dim() != 3 or x.shape[0] != 1:
+            raise ValueError("Paraformer.inference: one utterance x [1, T, F]")
+        T = _sub_len(x.shape[1])
+        if T < 1:
+            raise ValueError(f"Paraformer.inference: {x.shape[1]} frames subsample to none (Conv2d needs T >= 7)")
+        h, _ = decoding.encode(self, x, fp32=True)
+        plen = torch.full((1,), T, dtype=torch.int32, device=x.device)
+        mask = torch.zeros(1, T, dtype=torch.uint8, device=x.device)
+        cif, ulens, ids, logits = FN.paraformer_decode(self, h, plen, mask, 1, T)
+        self.last_decode = SimpleNamespace(cif=cif, ulens=ulens, logits=logits, h=h)
+        return [] if ids is None else ids[0, :ulens[0]].tolist()
 
     def get_pred_len(self, xlens) -> Tensor:
         """paraformer.py:122-124."""

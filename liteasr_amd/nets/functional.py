@@ -1132,6 +1132,52 @@ class HeadsFn(torch.autograd.Function):
         return dx, None, None, None
 
 
+def predictor_logits(pr, hm, B, T):
+    """The predictor's logits (predictor.py:32-33 before the sigmoid): conv1d(k3, pad 1) as
+    one GEMM over overlapping row windows of a zero-padded copy, then the scalar head.
+    hm [B*T, d] in the compute dtype -> (z [B*T, 1] fp32, xpad, cv: what the backward keeps)."""
+    dev, adt = hm.device, hm.dtype
+    d = hm.shape[-1]
+    M = B * T
+    wp = pr.weights()
+    xpad = torch.zeros(B, T + 2, d, dtype=adt, device=dev)
+    xpad[:, 1:T + 1] = hm.view(B, T, d)
+    wc = _e((d, 3 * d), adt, dev)
+    K.permute_last2(wp.Wc.reshape(d, d, 3), d, d, 3, wc)  # [out][in][tap] -> [out][tap][in]
+    win = xpad.as_strided((B, T, 3 * d), ((T + 2) * d, d, 1))
+    cv = _e((B, T, d), adt, dev)
+    K.gemm(win, wc.t().unsqueeze(0).expand(B, 3 * d, d), cv, bias=wp.bc, act=ACT_RELU)
+    z = _e((M, 1), F32, dev)
+    K.gemm(cv.view(M, d), wp.Wl.t(), z, bias=wp.bl)
+    return z, xpad, cv
+
+
+def paraformer_decode(model, h32, plen, mask_k, B, T):
+    """Paraformer's one-pass decoding after the encoder (liteasr/models/paraformer.py:126-128,
+    the predictor in its inference branch, predictor.py:41-53): h32 [B*T, d] fp32 encoder
+    output, plen int32 [B] frames the predictor keeps, mask_k u8 [B, T] the memory key mask
+    (1 = padding).  Returns (cif: the K.cif_infer state, ulens: host list, ids: host int32
+    [B, L] with L = max ulens, logits [B*L, V]); ids and logits are None when L = 0.  One
+    device->host copy of ulen [B] sizes the decoder pass (the reference's max(ulens)); the
+    decoder's self-attention over the L rows is unmasked, as in the reference."""
+    dev, adt = h32.device, model.compute_dtype
+    dec = model.decoder
+    d = h32.shape[1]
+    hm = h32.to(adt)
+    z, _, _ = predictor_logits(model.predictor, hm, B, T)
+    cif = K.cif_infer(z, plen, h32.view(B, T, d))
+    ulens = cif.ulen.cpu().tolist()
+    L = max(ulens)
+    if L == 0:
+        return cif, ulens, None, None
+    nomask = torch.zeros(B, L, dtype=torch.uint8, device=dev)
+    rows = cif.out[:, :L].contiguous().view(B * L, d)
+    hat, _ = decoder_layers_fwd(dec, dec.weights(), rows, hm, B, L, T, (nomask, L, 0, mask_k),
+                                (0.0, 0.0, 0.0, 0.0), adt, seed_shift=8)
+    _, ids, _ = K.logsoftmax_topk(hat, 1)
+    return cif, ulens, ids.view(B, L).cpu(), hat
+
+
 @ranged
 class ParaformerHeadsFn(torch.autograd.Function):
     """Everything of Paraformer.forward after the conformer layers (liteasr/models/
@@ -1156,18 +1202,7 @@ class ParaformerHeadsFn(torch.autograd.Function):
         h32, me, re = _e((M, d), F32, dev), _e(M, F32, dev), _e(M, F32, dev)
         K.layernorm_fwd(x, we.g, we.b, LN_EPS, h32, me, re)
         hm = h32.to(adt)
-        # ---- predictor: conv1d(k3, pad 1) as one GEMM over overlapping row windows of a
-        # zero-padded copy, then the scalar head
-        wp = pr.weights()
-        xpad = torch.zeros(B, T + 2, d, dtype=adt, device=dev)
-        xpad[:, 1:T + 1] = hm.view(B, T, d)
-        wc = _e((d, 3 * d), adt, dev)
-        K.permute_last2(wp.Wc.reshape(d, d, 3), d, d, 3, wc)  # [out][in][tap] -> [out][tap][in]
-        win = xpad.as_strided((B, T, 3 * d), ((T + 2) * d, d, 1))
-        cv = _e((B, T, d), adt, dev)
-        K.gemm(win, wc.t().unsqueeze(0).expand(B, 3 * d, d), cv, bias=wp.bc, act=ACT_RELU)
-        z = _e((M, 1), F32, dev)
-        K.gemm(cv.view(M, d), wp.Wl.t(), z, bias=wp.bl)
+        z, xpad, cv = predictor_logits(pr, hm, B, T)
         # ---- CIF
         plen = env.pred_len
         ylen = env.ylen
