@@ -136,12 +136,20 @@ float lasr_dropout_scale(float p);
 int lasr_gemm_plan(const lasr_gemm_args* args, int* tile_m, int* tile_n, int* split_k, int* flags);
 
 /* Grouped split-K weight gradients (liteasr/trainer.py:142 loss.backward: the per-module
- * weight gradients of one Conformer layer / the decoder): n <= 8 independent partials-only
+ * weight gradients of one Conformer layer / the decoder): n <= 32 independent partials-only
  * problems dW_i = A_i^T B_i (args[i] as for lasr_gemm with split_k = -1: A M-contiguous,
  * B N-contiguous, bf16, no epilogue, workspace for [split][M][N] partials + [split][M]
  * rowsum partials when rowsum is set) that plan the same tile with 64-deep stages, in one
  * launch; the partials are bit-identical to separate lasr_gemm calls.  The caller reduces
- * them (lasr_reduce_multi). */
+ * them (lasr_reduce_multi).
+ * Serial-slice problems: split_k <= -2 (that many K slices, at most 64), workspace NULL,
+ * C fp32 with ldc >= N, beta 0 or 1, alpha 1.  The plan and the K slices are those of the
+ * partials-only problem with that split, but one workgroup per output tile runs the slices
+ * one after the other, sums them in slice order and writes C = sum (beta 0) or C = C + sum
+ * (beta 1) and rowsum[m] += the slices' row sums itself: the bits of the partials-only launch
+ * followed by lasr_reduce_multi, with no workspace touched.  Tiles: 64 x 64 plans, and the
+ * 64 x 128 / 128 x 64 plans with M, N >= 256 (256 x 128 group tiles); a launch is all serial
+ * or not at all, and its problems run in call order. */
 int lasr_gemm_dw_group(const lasr_gemm_args* args, int n, void* stream);
 /* Block order of later lasr_gemm_dw_group launches: 1 (default) = the problems with the
  * longest K slice first, 0 = call order; the partials are the same bits either way. */

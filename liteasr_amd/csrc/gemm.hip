@@ -323,7 +323,13 @@ int gemm_run(const lasr_gemm_args* a, void* stream, GemmRowPost* post) {
 // (split_k = -1) LDS-DMA launch with 64-deep stages, A M-contiguous and B N-contiguous
 // (dW = dY^T X), and all must share the planned tile; the partials (+ fused rowsum partials)
 // land exactly where lasr_gemm would put them, bit for bit.
-int launch_dw_group(const DwGroupP& g, int BM, int BN, int blocks, hipStream_t st);
+//
+// Serial-slice problems (split_k <= -2, no workspace, C set): the same plan and the same K
+// slices as the partials-only problem with that split, but one block per output tile runs the
+// slices one after the other, sums them in slice order and writes C = sum (beta 0) or
+// C = C + sum (beta 1) and rowsum += itself -- the bits of the slab launch followed by
+// lasr_reduce_multi, with no slab.  A launch is all serial or not at all.
+int launch_dw_group(const DwGroupP& g, int BM, int BN, int blocks, bool serial, hipStream_t st);
 static int dw_group_lpt = 1;  // (lasr_gemm_dw_group_order: tests and A/B runs)
 extern "C" int lasr_gemm_dw_group_order(int longest_first) {
   dw_group_lpt = longest_first != 0;
@@ -342,8 +348,18 @@ extern "C" int lasr_gemm_dw_group(const lasr_gemm_args* args, int n, void* strea
   // partials are bit-identical.
   int ord[LASR_DW_GROUP_MAX];
   int64_t work[LASR_DW_GROUP_MAX];
+  // a serial problem is planned as the partials-only problem it replaces (the planner asks
+  // for a workspace before it splits K; none is read or written)
+  auto planned = [](const lasr_gemm_args* a) {
+    lasr_gemm_args b = *a;
+    if (b.split_k <= -2 && !b.workspace) {
+      b.workspace = (void*)(uintptr_t)16;
+      b.workspace_bytes = INT64_MAX;
+    }
+    return b;
+  };
   for (int i = 0; i < n; ++i) {
-    const lasr_gemm_args* a = args + i;
+    const lasr_gemm_args pa = planned(args + i), *a = &pa;
     int bm, bn, sp, ks;
     gemm_plan(a, &bm, &bn, &sp, &ks);
     // the K slice each block runs (the exact split is settled below; the group's tile is
@@ -351,11 +367,14 @@ extern "C" int lasr_gemm_dw_group(const lasr_gemm_args* args, int n, void* strea
     work[i] = a->split_k == 1 || sp <= 1 ? a->K : cdiv(a->K, sp);
     ord[i] = i;
   }
-  if (dw_group_lpt)
+  // (serial problems run in queue order: their blocks all run a whole K)
+  if (dw_group_lpt && !(args[0].split_k <= -2 && !args[0].workspace))
     std::stable_sort(ord, ord + n, [&](int x, int y) { return work[x] > work[y]; });
   int BM0 = 0, BN0 = 0, blocks = 0;
+  bool all_serial = false;
   for (int i = 0; i < n; ++i) {
-    const lasr_gemm_args* a = args + ord[i];
+    const bool serial = args[ord[i]].split_k <= -2 && !args[ord[i]].workspace;
+    const lasr_gemm_args pa = planned(args + ord[i]), *a = &pa;
     LASR_CHECK_ARG(a->in_dtype == LASR_BF16 && a->c_dtype == LASR_F32, "lasr_gemm_dw_group: bf16 in, fp32 partials");
     LASR_CHECK_ARG(a->lda_m == 1 && a->lda_k != 1 && a->ldb_n == 1 && a->ldb_k != 1,
                    "lasr_gemm_dw_group: A M-contiguous and B N-contiguous (dW = dY^T X)");
@@ -363,6 +382,11 @@ extern "C" int lasr_gemm_dw_group(const lasr_gemm_args* args, int n, void* strea
     LASR_CHECK_ARG((direct || (a->split_k < 0 && a->workspace)) && (a->batch <= 1) && a->M > 0 && a->N > 0 &&
                        a->K > 0,
                    "lasr_gemm_dw_group: partials-only problems with a workspace, or direct (split_k 1) ones");
+    LASR_CHECK_ARG(!serial || (a->C && a->ldc >= a->N && (a->beta == 0.f || a->beta == 1.f) && a->alpha == 1.f &&
+                               !a->alpha_dev && a->split_k >= -64),
+                   "lasr_gemm_dw_group: a serial problem needs C, ldc >= N, beta 0 or 1, alpha 1, <= 64 slices");
+    LASR_CHECK_ARG(i == 0 || serial == all_serial, "lasr_gemm_dw_group: serial and slab problems mixed");
+    all_serial = serial;
     LASR_CHECK_ARG(!direct || (a->C && a->ldc >= a->N && (a->beta == 0.f || a->beta == 1.f) && a->alpha == 1.f &&
                                !a->alpha_dev),
                    "lasr_gemm_dw_group: a direct problem needs C, ldc >= N, beta 0 or 1, alpha 1");
@@ -401,20 +425,21 @@ extern "C" int lasr_gemm_dw_group(const lasr_gemm_args* args, int n, void* strea
     g.kchunk[i] = direct ? a->K : (int)(cdiv(cdiv(a->K, split), 32) * 32);
     g.direct[i] = direct;
     g.C[i] = (float*)a->C; g.ldc[i] = a->ldc; g.beta[i] = a->beta; g.rowsum[i] = a->rowsum;
-    g.v4[i] = a->N % 4 == 0 && aligned16(direct ? a->C : a->workspace);
+    g.v4[i] = serial ? a->N % 4 == 0 && aligned16(a->C) && a->ldc % 4 == 0
+                     : a->N % 4 == 0 && aligned16(direct ? a->C : a->workspace);
     g.A[i] = a->A; g.lda[i] = a->lda_k;
     g.B[i] = a->B; g.ldb[i] = a->ldb_k;
-    g.ws[i] = (float*)a->workspace;
-    g.rs_ws[i] = a->rowsum && !direct ? (float*)a->workspace + (int64_t)split * a->M * a->N : nullptr;
+    g.ws[i] = serial ? nullptr : (float*)a->workspace;
+    g.rs_ws[i] = a->rowsum && !direct && !serial ? (float*)a->workspace + (int64_t)split * a->M * a->N : nullptr;
     g.start[i] = blocks;
-    const int64_t nb = cdiv(a->M, BM) * cdiv(a->N, BN) * (int64_t)split;
+    const int64_t nb = cdiv(a->M, BM) * cdiv(a->N, BN) * (int64_t)(serial ? 1 : split);
     LASR_CHECK_ARG(blocks + nb + 8 < (1ll << 31), "lasr_gemm_dw_group: too many blocks");
     blocks += (int)cdiv(nb, 8) * 8;
   }
   g.start[n] = blocks;
   static const int slice_xcd = [] { const char* e = getenv("LASR_DW_SLICE_XCD"); return e && e[0] ? atoi(e) : 1; }();
   g.slice_xcd = slice_xcd;
-  LASR_CHECK_ARG(launch_dw_group(g, BM0, BN0, blocks, (hipStream_t)stream) == 0,
+  LASR_CHECK_ARG(launch_dw_group(g, BM0, BN0, blocks, all_serial, (hipStream_t)stream) == 0,
                  "lasr_gemm_dw_group: no grouped instance for tile %dx%d", BM0, BN0);
   return lasr_check_launch("lasr_gemm_dw_group");
 }

@@ -656,6 +656,43 @@ LASR_DEV void gemm_epilogue_direct(const GemmP& p, f32x4 (&acc)[BM / 32][BN / (8
   }
 }
 
+// Epilogue of a serial-slice weight-gradient tile (gemm_glds_tile SERIAL): tot holds the slice
+// sums in gemm_epilogue_direct's lane layout; C = tot (beta 0) or C = C + tot (beta 1, the
+// reduction's c + acc), fp32, 16-B accesses where the row allows.
+template <int BM, int BN, int NW>
+LASR_DEV void gemm_epilogue_serial(const GemmP& p, f32x4 (&tot)[BM / 32][BN / (8 * NW)], int m0, int n0) {
+  constexpr int WCOLS = NW / 2;
+  constexpr int WM = BM / 2, WN = BN / WCOLS, FM = WM / 16, FN = WN / 16;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int wr = wid / WCOLS, wc = wid % WCOLS;
+  const int mr = m0 + wr * WM + (lane & 15), nc = n0 + wc * WN + 4 * (lane >> 4);
+  const bool accum = p.beta != 0.f;
+  float* C = (float*)p.C;
+#pragma unroll
+  for (int i = 0; i < FM; ++i) {
+    const int m = mr + i * 16;
+    if (m >= p.M) continue;
+#pragma unroll
+    for (int j = 0; j < FN; ++j) {
+      const int n = nc + j * 16;
+      if (n >= p.N) continue;
+      float* dst = C + (int64_t)m * p.ldc + n;
+      float a[4] = {tot[i][j][0], tot[i][j][1], tot[i][j][2], tot[i][j][3]};
+      if (p.v4 && n + 4 <= p.N) {
+        if (accum) {
+          float c[4];
+          ldv<4>(dst, c);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) a[q] = c[q] + a[q];
+        }
+        stv<4>(dst, a);
+      } else {
+        for (int q = 0; q < 4 && n + q < p.N; ++q) dst[q] = accum ? dst[q] + a[q] : a[q];
+      }
+    }
+  }
+}
+
 // Epilogue of the conv2 data gradient fused with conv1's weight gradient (EPI_AUX_RELU_W1,
 // BM x 256 tiles, 4 waves): dy1 = bf16(acc) * relu'(y1) -- exactly the values the plain G_DX
 // epilogue stores -- is never written; the tile's partial of dW1 [C][9] / db1 [C] is formed
@@ -868,10 +905,20 @@ LASR_DEV int xcd_remap(int orig, int nwg) {
 
 // One output tile (tx, ty) of K slice / batch index zz: the body shared by the launch-grid
 // kernel (gemm_bf16_glds_kernel) and the grouped weight-gradient kernel (gemm_dw_group_kernel).
-template <int BM, int BN, bool AKC, bool BKC, typename TC, int S, int G, int KS, int NW = 4, int EPI = EPI_RT>
+//
+// SERIAL (the grouped weight-gradient kernel's serial-slice problems): the block owns the tile
+// and runs the split_k K slices one after the other, each through the very slice loop below
+// (same ring prologue, sub-tile order and ragged tail, so each slice accumulator holds the
+// bits of the slab p_s a split-K block would have stored), sums them in slice order as
+// lasr_reduce_multi does (t = 0; t += p_0; t += p_1; ...) and writes C = t or C = C + t itself
+// (gemm_epilogue_serial); the fused bias row sums likewise.  No workspace is touched.
+template <int BM, int BN, bool AKC, bool BKC, typename TC, int S, int G, int KS, int NW = 4, int EPI = EPI_RT,
+          bool SERIAL = false>
 LASR_DEV void gemm_glds_tile(const GemmP& p, const int tx, const int ty, const int zz) {
   static_assert(G == G_LIN || (G == G_DW ? (!AKC && !BKC) : (AKC && (G == G_FWD) == BKC)),
                 "gather instance operand orientation");
+  static_assert(!SERIAL || (G == G_LIN && !AKC && !BKC && std::is_same<TC, float>::value && EPI == EPI_RT),
+                "serial slices: fp32 weight gradients only");
   static_assert(KS == 1 || KS == 2, "k sub-tiles per ring stage");
   static_assert(NW == 4 || NW == 8, "4 waves (2 x 2) or 8 waves (2 x 4)");
   constexpr int BK = 32;
@@ -887,14 +934,16 @@ LASR_DEV void gemm_glds_tile(const GemmP& p, const int tx, const int ty, const i
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wr = wid / WCOLS, wc = wid % WCOLS;
 
-  const int s = zz % p.split_k, z = zz / p.split_k;
+  // (s and its k range are per slice: set once here, again per slice when SERIAL)
+  int s = SERIAL ? 0 : zz % p.split_k;
+  const int z = SERIAL ? 0 : zz / p.split_k;
   const int z1 = z / p.batch_div, z2 = z % p.batch_div;
   const bf16_t* A = (const bf16_t*)p.A + z1 * p.sa1 + z2 * p.sa2;
   const bf16_t* B = (const bf16_t*)p.B + z1 * p.sb1 + z2 * p.sb2;
   const int m0 = ty * BM, n0 = tx * BN;
-  const int kbeg = s * p.kchunk;
-  const int kend = min(p.K, kbeg + p.kchunk);
-  const int nk = kend > kbeg ? (kend - kbeg + BK - 1) / BK : 0;
+  int kbeg = s * p.kchunk;
+  int kend = min(p.K, kbeg + p.kchunk);
+  int nk = kend > kbeg ? (kend - kbeg + BK - 1) / BK : 0;
   const int64_t lda = AKC ? p.lda_m : p.lda_k, ldb = BKC ? p.ldb_n : p.ldb_k;
 
   f32x4 acc[FM][FN];
@@ -905,7 +954,7 @@ LASR_DEV void gemm_glds_tile(const GemmP& p, const int tx, const int ty, const i
 
   // full 32-deep tiles go through the glds ring; a ragged last tile is handled after the
   // loop (ordinary loads inside the loop would make hipcc drain the ring with vmcnt(0))
-  const int nfull = (kend - kbeg) > 0 ? (kend - kbeg) / BK : 0;
+  int nfull = (kend - kbeg) > 0 ? (kend - kbeg) / BK : 0;
   [[maybe_unused]] ConvRowsKC<BM, NT> ga;
   [[maybe_unused]] ConvRowsDW<BN, NT> gb;
   if constexpr (G == G_FWD) ga.init_fwd(p.cv, m0, p.M, tid);
@@ -1019,69 +1068,106 @@ LASR_DEV void gemm_glds_tile(const GemmP& p, const int tx, const int ty, const i
 #pragma unroll
   for (int q = 0; q < 8; ++q) rs[q] = 0.f;
 
-  const int nst = nfull / KS;  // full ring stages; KS > 1 leaves nfull % KS sub-tiles
+  // SERIAL: the sum of the tile's slices, in slice order
+  [[maybe_unused]] f32x4 tot[SERIAL ? FM : 1][SERIAL ? FN : 1];
+  [[maybe_unused]] float rs_tot = 0.f;  // (thread tid < BM: row m0 + tid)
+  if constexpr (SERIAL)
 #pragma unroll
-  for (int t = 0; t < S - 1; ++t)
-    if (t < nst) issue(t);
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+      for (int j = 0; j < FN; ++j) tot[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  // one K slice [kbeg, kend) into acc (+ its bias row sums) per pass; a single pass unless SERIAL
+  [[maybe_unused]] int sl = 0;
+  do {
+    if constexpr (SERIAL) {
+      s = sl;
+      kbeg = s * p.kchunk;
+      kend = min(p.K, kbeg + p.kchunk);
+      nk = kend > kbeg ? (kend - kbeg + BK - 1) / BK : 0;
+      nfull = (kend - kbeg) > 0 ? (kend - kbeg) / BK : 0;
+#pragma unroll
+      for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int j = 0; j < FN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int q = 0; q < 8; ++q) rs[q] = 0.f;
+    }
+    const int nst = nfull / KS;  // full ring stages; KS > 1 leaves nfull % KS sub-tiles
+#pragma unroll
+    for (int t = 0; t < S - 1; ++t)
+      if (t < nst) issue(t);
 
-  for (int kt = 0; kt < nst; ++kt) {
-    const int after = min(S - 2, nst - 1 - kt);  // stages issued after kt (still in flight)
-    wait_ring<S, GL * KS>(after);
-    lds_barrier();
-    if (kt + S - 1 < nst) issue(kt + S - 1);
-#pragma unroll
-    for (int u = 0; u < KS; ++u) compute(smem + (kt % S) * STAGE + u * TILE);
-    if constexpr (!AKC)
-      if (do_rs)
-#pragma unroll
-        for (int u = 0; u < KS; ++u) rowsum_tile<BM, NT>(smem + (kt % S) * STAGE + u * TILE, tid, rs);
-  }
-  if constexpr (KS > 1) {
-    // leftover full sub-tile(s): the loop's last wait was vmcnt(0), so no DMA is in flight
-    for (int j = nst * KS; j < nfull; ++j) {
-      __syncthreads();
-      issue_sub(kbeg + j * BK, smem);
-      wait_vmcnt<0>();
+    for (int kt = 0; kt < nst; ++kt) {
+      const int after = min(S - 2, nst - 1 - kt);  // stages issued after kt (still in flight)
+      wait_ring<S, GL * KS>(after);
       lds_barrier();
+      if (kt + S - 1 < nst) issue(kt + S - 1);
+#pragma unroll
+      for (int u = 0; u < KS; ++u) compute(smem + (kt % S) * STAGE + u * TILE);
+      if constexpr (!AKC)
+        if (do_rs)
+#pragma unroll
+          for (int u = 0; u < KS; ++u) rowsum_tile<BM, NT>(smem + (kt % S) * STAGE + u * TILE, tid, rs);
+    }
+    if constexpr (KS > 1) {
+      // leftover full sub-tile(s): the loop's last wait was vmcnt(0), so no DMA is in flight
+      for (int j = nst * KS; j < nfull; ++j) {
+        __syncthreads();
+        issue_sub(kbeg + j * BK, smem);
+        wait_vmcnt<0>();
+        lds_barrier();
+        compute(smem);
+        if constexpr (!AKC)
+          if (do_rs) rowsum_tile<BM, NT>(smem, tid, rs);
+      }
+    }
+    if (G == G_LIN && nfull < nk) {  // ragged tail: register loader with zero fill (conv: host-checked K % 32 == 0)
+      __syncthreads();
+      TileLoader<BM, AKC, NT> la;
+      TileLoader<BN, BKC, NT> lb;
+      const int k0 = kbeg + nfull * BK;
+      la.load(A, AKC ? p.lda_m : 0, AKC ? 0 : p.lda_k, m0, p.M, k0, kend, true, tid);
+      lb.load(B, BKC ? p.ldb_n : 0, BKC ? 0 : p.ldb_k, n0, p.N, k0, kend, true, tid);
+      la.store(smem, tid);
+      lb.store(smem + BM * BK, tid);
+      __syncthreads();
       compute(smem);
       if constexpr (!AKC)
         if (do_rs) rowsum_tile<BM, NT>(smem, tid, rs);
     }
-  }
-  if (G == G_LIN && nfull < nk) {  // ragged tail: register loader with zero fill (conv: host-checked K % 32 == 0)
     __syncthreads();
-    TileLoader<BM, AKC, NT> la;
-    TileLoader<BN, BKC, NT> lb;
-    const int k0 = kbeg + nfull * BK;
-    la.load(A, AKC ? p.lda_m : 0, AKC ? 0 : p.lda_k, m0, p.M, k0, kend, true, tid);
-    lb.load(B, BKC ? p.ldb_n : 0, BKC ? 0 : p.ldb_k, n0, p.N, k0, kend, true, tid);
-    la.store(smem, tid);
-    lb.store(smem + BM * BK, tid);
-    __syncthreads();
-    compute(smem);
-    if constexpr (!AKC)
-      if (do_rs) rowsum_tile<BM, NT>(smem, tid, rs);
-  }
-  __syncthreads();
-  if constexpr (!AKC) {
-    if (do_rs) {  // combine the k groups in fixed order, then one slot per row
-      constexpr int CH = BM / 8, KG = NT / CH;
-      float* red = reinterpret_cast<float*>(smem_epi);
-      const int c = tid % CH, kg = tid / CH;
+    if constexpr (!AKC) {
+      if (do_rs) {  // combine the k groups in fixed order, then one slot per row
+        constexpr int CH = BM / 8, KG = NT / CH;
+        float* red = reinterpret_cast<float*>(smem_epi);
+        const int c = tid % CH, kg = tid / CH;
 #pragma unroll
-      for (int q = 0; q < 8; ++q) red[kg * BM + 8 * c + q] = rs[q];
-      __syncthreads();
-      if (tid < BM) {
-        float t = 0.f;
-        for (int g = 0; g < KG; ++g) t += red[g * BM + tid];
-        const int m = m0 + tid;
-        if (m < p.M) {
-          if (p.split_k > 1) p.rs_ws[(int64_t)s * p.M + m] = t;
-          else p.rowsum[m] += t;
+        for (int q = 0; q < 8; ++q) red[kg * BM + 8 * c + q] = rs[q];
+        __syncthreads();
+        if (tid < BM) {
+          float t = 0.f;
+          for (int g = 0; g < KG; ++g) t += red[g * BM + tid];
+          const int m = m0 + tid;
+          if constexpr (SERIAL) {
+            rs_tot += t;
+          } else if (m < p.M) {
+            if (p.split_k > 1) p.rs_ws[(int64_t)s * p.M + m] = t;
+            else p.rowsum[m] += t;
+          }
         }
+        __syncthreads();
       }
-      __syncthreads();
     }
+    if constexpr (SERIAL)
+#pragma unroll
+      for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int j = 0; j < FN; ++j) tot[i][j] += acc[i][j];
+  } while (SERIAL && ++sl < p.split_k);
+  if constexpr (SERIAL) {
+    if (do_rs && tid < BM && m0 + tid < p.M) p.rowsum[m0 + tid] += rs_tot;
+    gemm_epilogue_serial<BM, BN, NW>(p, tot, m0, n0);
+    return;
   }
   if constexpr (W1) {
     dx_w1_epilogue<BM, BN, NW>(p, acc, smem_epi, m0, n0, dxrow, xr);
@@ -1122,7 +1208,14 @@ __global__ __launch_bounds__(NW * 64, MINB * NW / 4) void gemm_bf16_glds_kernel(
 // launch grid of the single-problem kernel; the tile code and the partial layout
 // ([split][M][N] + [split][M] rowsum partials) are those of gemm_bf16_glds_kernel, so the
 // partials are bit-identical to separate launches.
-#define LASR_DW_GROUP_MAX 8
+//
+// Serial-slice launches (SERIAL; every problem of the launch): problem i owns one block per
+// output tile ([start[i], start[i+1]), tiles in the same dw_tile_order / XCD remap), and the
+// block runs the tile's split[i] K slices itself (gemm_glds_tile SERIAL) and writes C / rowsum
+// directly: the bits of the slab launch followed by lasr_reduce_multi, with no slab.
+//
+// 32 problems = 3.5 KB of kernel arguments (under the 4 KB kernarg budget).
+#define LASR_DW_GROUP_MAX 32
 struct DwGroupP {
   int n;
   int start[LASR_DW_GROUP_MAX + 1];
@@ -1136,6 +1229,7 @@ struct DwGroupP {
   int slice_xcd;                    // K slices tied to XCDs (gemm_dw_group_kernel)
   // direct problems (split 1): full-K tiles that write the weight gradient itself (C = beta C +
   // dY^T X, fp32) and add their bias rowsum into rowsum -- no partial slab, no reduction
+  // (C, ldc, beta, rowsum also serve the serial-slice problems)
   int direct[LASR_DW_GROUP_MAX];
   float* C[LASR_DW_GROUP_MAX];
   int64_t ldc[LASR_DW_GROUP_MAX];
@@ -1143,7 +1237,7 @@ struct DwGroupP {
   float* rowsum[LASR_DW_GROUP_MAX];
 };
 
-template <int BM, int BN, int S, int MINB, int NW = 4>
+template <int BM, int BN, int S, int MINB, int NW = 4, bool SERIAL = false>
 __global__ __launch_bounds__(NW * 64, MINB * NW / 4) void gemm_dw_group_kernel(DwGroupP g) {
   const int blk = blockIdx.x;
   int i = 0;
@@ -1151,7 +1245,7 @@ __global__ __launch_bounds__(NW * 64, MINB * NW / 4) void gemm_dw_group_kernel(D
     if (blk >= g.start[j]) i = j;
   const int ntx = (g.N[i] + BN - 1) / BN, nty = (g.M[i] + BM - 1) / BM, ntile = ntx * nty;
   const int local = blk - g.start[i];
-  if (local >= ntile * g.split[i]) return;  // alignment padding
+  if (local >= (SERIAL ? ntile : ntile * g.split[i])) return;  // alignment padding
   GemmP p = {};
   p.M = g.M[i]; p.N = g.N[i]; p.K = g.K[i]; p.batch = 1; p.batch_div = 1;
   p.A = g.A[i]; p.lda_m = 1; p.lda_k = g.lda[i];
@@ -1165,6 +1259,14 @@ __global__ __launch_bounds__(NW * 64, MINB * NW / 4) void gemm_dw_group_kernel(D
     p.rowsum = g.rowsum[i]; p.rs_ws = nullptr; p.ws = nullptr;
     p.c_vec = ((uintptr_t)p.C & 15) == 0 && p.ldc % 8 == 0;
     p.epi_mode = p.c_vec && p.beta == 0.f ? 0 : 2;
+  }
+  if constexpr (SERIAL) {  // one block per tile, all its K slices; no workspace
+    p.C = g.C[i]; p.ldc = g.ldc[i]; p.beta = g.beta[i];
+    p.rowsum = g.rowsum[i]; p.rs_ws = nullptr; p.ws = nullptr;
+    int tx, ty;
+    dw_tile_order(xcd_remap(local, ntile), ntx, nty, p.N > p.M, tx, ty);
+    gemm_glds_tile<BM, BN, false, false, float, S, G_LIN, 2, NW, EPI_RT, true>(p, tx, ty, 0);
+    return;
   }
   // Block -> (tile, K slice).  The hardware deals blocks to the 8 XCDs round-robin (block % 8;
   // problem ranges start at multiples of 8).  When the split divides 8 and the tiles divide

@@ -75,6 +75,9 @@ class _Deferred:
         self.gemms = []  # queued partials-only dW GEMMs: (tile key, args, operand refs)
         self.held = []  # reductions of finished `hold` blocks, not yet launched
         self.done = []  # their on_done callbacks, in block order
+        self.holding = False  # inside an outermost hold block
+        self.held_gemms = []  # dW GEMMs of finished `hold` blocks, not yet launched (no slab yet)
+        self.held_layers = 0  # hold blocks whose GEMMs wait in held_gemms
 
 
 _DEFER = _Deferred()
@@ -86,16 +89,21 @@ def deferred_reductions(hold=False, on_done=None):
     GEMMs (split_k=0, beta 0 or 1, fp32 contiguous C) are only complete after the block
     exits; nothing inside may read them.  on_done() runs once they are complete.
 
-    hold=True (the encoder layers' backward nodes): the grouped weight-gradient launches still
-    run at the end of the block, but its reductions wait in a queue (their partial buffers
-    alive) for the next block that does not hold, or flush_reductions(): the reductions of
-    several layers then share lasr_reduce_multi launches, each with its usual summation order,
-    and the held blocks' on_done callbacks run after them, in order.
+    hold=True (the encoder layers' backward nodes): the block's reductions wait in a queue
+    (their partial buffers alive) for the next block that does not hold, or flush_reductions():
+    the reductions of several layers then share lasr_reduce_multi launches, each with its usual
+    summation order, and the held blocks' on_done callbacks run after them, in order.  Its
+    grouped weight-gradient GEMMs wait too (DW_HOLD_GEMMS; their operands alive, so the caller
+    must not modify them before that flush): they launch there, before the reductions, in
+    queue order, and a family with enough tiles by then runs serial-slice, without slabs
+    (_flush_held_gemms).  A held block that raises drops its waiting GEMMs unlaunched.
 
     Only an outermost block can hold or take a callback (its end is where reductions are
     launched or queued): asking for either inside another block raises."""
     if _DEFER.depth and (hold or on_done is not None):
         raise RuntimeError("deferred_reductions: hold / on_done inside another deferred block would be dropped")
+    if _DEFER.depth == 0:
+        _DEFER.holding = bool(hold)
     _DEFER.depth += 1
     ok = False
     try:
@@ -104,6 +112,9 @@ def deferred_reductions(hold=False, on_done=None):
     finally:
         _DEFER.depth -= 1
         if _DEFER.depth == 0:
+            _DEFER.holding = False
+            waiting = [q for q in _DEFER.gemms if _waits(q)]
+            _DEFER.gemms = [q for q in _DEFER.gemms if not _waits(q)]
             if hold and ok:
                 if _DEFER.gemms:
                     _flush_gemm_group()
@@ -111,15 +122,24 @@ def deferred_reductions(hold=False, on_done=None):
                 _DEFER.segs = []
                 if on_done is not None:
                     _DEFER.done.append(on_done)
+                if waiting:
+                    _DEFER.held_gemms.extend(waiting)
+                    _DEFER.held_layers += 1
+                    if DW_HOLD_LAYERS and _DEFER.held_layers >= DW_HOLD_LAYERS:
+                        _flush_held_gemms()
             else:
+                # the block that ends the hold (a segment's lowest layer) adds its own GEMMs to
+                # the families it flushes; a raising block's are dropped here, unlaunched
+                if ok:
+                    _DEFER.held_gemms.extend(waiting)
                 if on_done is not None:
                     _DEFER.done.append(on_done)
                 flush_reductions()
 
 
 def held_reductions():
-    """Number of reductions queued by hold blocks and not yet launched."""
-    return len(_DEFER.held)
+    """Number of reductions and weight-gradient GEMMs queued by hold blocks and not yet launched."""
+    return len(_DEFER.held) + len(_DEFER.held_gemms)
 
 
 def _defer(part, P, Ncols, out0, out1=None, split=None, accumulate=True):
@@ -128,7 +148,7 @@ def _defer(part, P, Ncols, out0, out1=None, split=None, accumulate=True):
 
 
 # Grouped weight gradients: dW GEMMs marked group=True inside a deferred_reductions block are
-# queued and launched at its end, one lasr_gemm_dw_group launch per planned tile (<= 8
+# queued and launched at its end, one lasr_gemm_dw_group launch per planned tile (<= 32
 # problems each), before the reductions (tests set DW_GROUP = False to compare with lone launches).
 DW_GROUP = True
 # plan tile -> group (lasr_gemm_dw_group runs the 64 x 128 / 128 x 64 plans, the FFN-sized
@@ -156,7 +176,66 @@ SMALL_GRID_TILES = 128  # (64 x 64 tiles below which a K >= 1024 GEMM is split)
 def _group_div(key):
     d = DW_GROUP_SPLIT_DIV
     return d.get(key, 1) if isinstance(d, dict) else d
-_GROUP_MAX = 8
+_GROUP_MAX = 32  # problems per lasr_gemm_dw_group launch (LASR_DW_GROUP_MAX)
+
+# Held weight-gradient GEMMs: inside a hold block the grouped dW GEMMs are queued without a
+# slab and launched where the held reductions are (tests set False to compare).
+DW_HOLD_GEMMS = True
+# A held family (one group tile) whose tiles at the flush fill the chip (>= the CU count) runs
+# serial-slice: one block per tile runs the planned K slices in order and writes the gradient
+# itself, the bits of slabs + lasr_reduce_multi.  Smaller families get their slabs
+# at the flush and take the slab path.  Counts only: the same on every step and rank.
+DW_SERIAL_MIN_TILES = 256
+# the waiting GEMMs are launched after this many hold blocks even inside a segment; 0 = at the
+# segment's end only.  4 layers of the small model are one full round of FFN tiles (256) and
+# measured best of 4 / 6 / whole segment on small, large and long (DESIGN §4,
+# profiles/r07/dw_held_serial_ab.jsonl)
+DW_HOLD_LAYERS = 4
+
+
+def _waits(q):
+    """A queued dW GEMM that has no slab yet (queued inside a hold block)."""
+    return q[1].split_k <= -2 and not q[1].workspace
+
+
+def _serial_tiles(key, M, Nn):
+    """Output tiles of a problem on its family's group tile (lasr_gemm_dw_group)."""
+    if key == (64, 64):
+        return -(-M // 64) * -(-Nn // 64)
+    if M >= 256 and Nn >= 256:
+        return -(-M // 256) * -(-Nn // 128)
+    return -(-M // 128) * -(-Nn // 128)
+
+
+def _flush_held_gemms():
+    """Launch the hold blocks' waiting dW GEMMs, family by family in queue order."""
+    q, _DEFER.held_gemms = _DEFER.held_gemms, []
+    _DEFER.held_layers = 0
+    _set_dw_order()
+    byt = {}
+    for key, args, refs in q:
+        byt.setdefault(key, []).append((args, refs))
+    for key, lst in byt.items():
+        chunks = [lst[i:i + _GROUP_MAX] for i in range(0, len(lst), _GROUP_MAX)]
+        tiles = [sum(_serial_tiles(key, a.M, a.N) for a, _ in ch) for ch in chunks]
+        # (every launch but a family's last fills the chip; the 128 x 128 tile of an FFN-family
+        # problem narrower than 256 has no serial instance)
+        serial = (sum(tiles) >= DW_SERIAL_MIN_TILES and all(t >= DW_SERIAL_MIN_TILES for t in tiles[:-1])
+                  and (key == (64, 64) or all(a.M >= 256 and a.N >= 256 for a, _ in lst)))
+        if not serial:
+            # the slab path: the partial buffers are made here and reduced with the held reductions
+            for args, (a, b, c, rowsum) in lst:
+                sp, M, Nn = -args.split_k, args.M, args.N
+                nrs = (sp + 128) * M if rowsum is not None else 0
+                part = torch.empty(sp * M * Nn + nrs, dtype=torch.float32, device=c.device)
+                args.workspace, args.workspace_bytes = ptr(part), part.numel() * 4
+                _DEFER.held.append((part, sp, M * Nn, c, None, M * Nn, int(args.beta == 1.0)))
+                if rowsum is not None:
+                    _DEFER.held.append((part[sp * M * Nn:], sp, M, rowsum, None, M, 1))
+        for ch in chunks:
+            arr = (N.GemmArgs * len(ch))(*[a for a, _ in ch])
+            N.call("lasr_gemm_dw_group", arr, len(ch), stream())
+    # the operand references in q die here, after the launches were enqueued
 
 
 # grouped dW blocks laid out longest K slice first (lasr_gemm_dw_group_order; same bits)
@@ -164,11 +243,15 @@ DW_GROUP_LPT = True
 _dw_order_set = [None]
 
 
-def _flush_gemm_group():
-    q, _DEFER.gemms = _DEFER.gemms, []
+def _set_dw_order():
     if _dw_order_set[0] != DW_GROUP_LPT:
         N.call("lasr_gemm_dw_group_order", int(DW_GROUP_LPT))
         _dw_order_set[0] = DW_GROUP_LPT
+
+
+def _flush_gemm_group():
+    q, _DEFER.gemms = _DEFER.gemms, []
+    _set_dw_order()
     byt = {}
     for key, args, refs in q:
         byt.setdefault(key, []).append(args)
@@ -191,6 +274,8 @@ def _flush_node_end(segs):
 
 
 def flush_reductions():
+    if _DEFER.held_gemms:  # before the reductions: the slab families' segments join _DEFER.held
+        _flush_held_gemms()
     segs = _DEFER.held + _DEFER.segs
     _DEFER.held, _DEFER.segs = [], []
     done, _DEFER.done = _DEFER.done, []
@@ -260,7 +345,8 @@ def gemm(
 
     group=True (a split-K weight gradient inside deferred_reductions): the launch itself may
     be deferred to the end of the block and grouped with the block's other dW GEMMs, so
-    the caller must not modify a or b before the block exits.
+    the caller must not modify a or b before the block exits (a hold block: before the held
+    reductions are flushed; the queue keeps a, b, c and rowsum referenced until then).
 
     ln_fwd=(gamma, beta, eps, y, mean, rstd): the LayerNorm of c's rows follows
     (lasr_gemm_ln_fwd: in the split-K reduction launch when K is split).  ln_bwd=lnb (an
@@ -354,6 +440,16 @@ def gemm(
             args.split_k = -sp
             N.call("lasr_gemm_plan", C.byref(args), C.byref(tm), C.byref(tn), C.byref(C.c_int()), C.byref(fl))
             grouped = (tm.value, tn.value) in _GROUP_TILES and bool(fl.value & 1)
+        if (sp > 1 and grouped and (_DEFER.holding or _DEFER.held_gemms) and DW_HOLD_GEMMS and sp <= 64
+                and (M * Nn) % 4 == 0 and (rowsum is None or (M % 4 == 0 and fl.value & 2))):
+            # a hold block: the GEMM waits, without a slab, for the flush of the held reductions
+            # (_flush_held_gemms: serial-slice, or the slab path with the slab made there).  The
+            # shapes kept out are those whose reduction is not lasr_reduce_multi's slice-order sum.
+            args.split_k = -sp
+            args.workspace, args.workspace_bytes = None, 0
+            key = _GROUP_TILES[(tm.value, tn.value)]
+            _DEFER.gemms.append((key, N.GemmArgs.from_buffer_copy(args), (a, b, c, rowsum)))
+            return c
         if sp > 1:
             # partials-only launch (split_k = -1) into a buffer that lives until the flush
             # rowsum partials (fused) or the column-sum scratch (unfused, fp32 operands)
