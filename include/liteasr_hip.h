@@ -750,6 +750,90 @@ int64_t lasr_rnnt_search_workspace(int Tcap, int layers, int H, int J, int V, in
 int lasr_rnnt_search_init(const lasr_rnnt_search_args* a, int Tp, void* stream);
 int lasr_rnnt_search_expand(const lasr_rnnt_search_args* a, int mode, void* stream);
 
+/* ---- wav2vec 2.0 pretraining (csrc/w2v.hip) -----------------------------------------
+ * Activations are channels-last: [B][T][C].  `dtype` arguments are LASR_F32 / LASR_BF16.
+ * Every parameter-gradient output ACCUMULATES (+=) in a fixed summation order; no entry
+ * uses floating-point atomics, so two runs give the same bits.
+ *
+ * Feature extractor layer 0 (liteasr/nets/wav2vec2_convolution.py:20,27: Conv1d(1, C, k, s),
+ * no padding): x [B][T_in] fp32, w [C][k] fp32, bias [C] or NULL, y [B][T_out][C] fp32,
+ * T_out = (T_in - k) / s + 1.  dw [C][k] += sum_{b,t} dy[b,t,:] x[b, s t + j]; k <= 16;
+ * ws: lasr_w2v_conv0_dw_parts(B, T_out) * C * k floats.  No input gradient (the waveform). */
+int lasr_w2v_conv0_fwd(const float* x, int B, int T_in, int C, int k, int s, const float* w,
+                       const float* bias, float* y, void* stream);
+int lasr_w2v_conv0_dw_parts(int B, int T_out);
+int lasr_w2v_conv0_dw(const float* x, const void* dy, int dy_dtype, int B, int T_in, int C, int k, int s,
+                      float* dw, float* ws, int64_t ws_floats, void* stream);
+/* LayerNorm over C with fp32 statistics, then the exact (erf) GELU when act = 1
+ * (wav2vec2_convolution.py:28-31: Fp32LayerNorm -> GELU; act = 0: wav2vec2.py:276, the model's
+ * layer_norm).  y = act(xhat gamma + beta); mean / rstd [rows] fp32 are kept for the backward,
+ * which recomputes the pre-activation.  Backward: C <= 1024; dgamma / dbeta accumulate;
+ * ws: ceil(rows / 64) * 2 * C floats. */
+int lasr_w2v_ln_act_fwd(const void* x, int x_dtype, int64_t rows, int C, const float* gamma, const float* beta,
+                        float eps, int act, void* y, int y_dtype, float* mean, float* rstd, void* stream);
+int lasr_w2v_ln_act_bwd(const void* x, int x_dtype, const void* dy, int dy_dtype, int64_t rows, int C,
+                        const float* gamma, const float* beta, const float* mean, const float* rstd, int act,
+                        void* dx, int dx_dtype, float* dgamma, float* dbeta, float* ws, int64_t ws_floats,
+                        void* stream);
+/* Input gradient of an extractor layer >= 1 (wav2vec2_convolution.py:20): dcol [B][T_out][k C]
+ * = dY W is folded back, dx [B][T_in][C] fp32 = sum over (t, j), s t + j = row, of dcol[b][t][j C + c]
+ * (rows no window covers get 0). */
+int lasr_w2v_col2im1d(const void* dcol, int dtype, int B, int T_in, int T_out, int C, int k, int s, float* dx,
+                      void* stream);
+/* Positional convolution (liteasr/nets/transformer_encoder.py:144-150,175-179: Conv1d(d, d, 128,
+ * padding 64, groups 16), last frame dropped, GELU, residual).  The GEMMs read a group-major,
+ * time-padded copy: pack writes dst [G][B][Tp][cg] = src [B][T][G cg] at rows front .. front + T - 1
+ * and zeros elsewhere, multiplied by GELU'(yg + bias) when yg [G][B][T][cg] is given (the
+ * backward's dY).  unpack: out [B][T][G cg] fp32 = res + act(yg + bias) (res / bias may be
+ * NULL; act 1 = GELU).  colsum: out[g cg + c] += sum of x [G][rows][cg] over rows (the bias
+ * gradient). */
+int lasr_w2v_group_pack(const float* src, int B, int T, int G, int cg, int front, int Tp, const void* yg,
+                        int yg_dtype, const float* bias, void* dst, int dst_dtype, void* stream);
+int lasr_w2v_group_unpack(const void* yg, int yg_dtype, const float* bias, int act, const float* res, int B, int T,
+                          int G, int cg, float* out, void* stream);
+int lasr_w2v_group_colsum(const void* x, int dtype, int G, int64_t rows, int cg, float* out, void* stream);
+/* Mask embedding (liteasr/models/wav2vec2.py:319-334): midx [B][M] int32, the masked frames of
+ * each utterance (distinct within an utterance).  fwd overwrites rows x[b][midx[b][m]] of
+ * x [B][T][d] fp32 with mask_emb; bwd adds those rows of dx to dmask_emb in (b, m) order and
+ * zeroes them.  gather: dst [B][M][d] = src[b stride_b + midx stride_t + c] (wav2vec2.py:289,293);
+ * scatter is its transpose into dst fp32 (accumulate 0: plain store; the caller zeroes the rest). */
+int lasr_w2v_mask_fwd(float* x, const int32_t* midx, int B, int T, int M, int d, const float* mask_emb,
+                      void* stream);
+int lasr_w2v_mask_bwd(float* dx, const int32_t* midx, int B, int T, int M, int d, float* dmask_emb, void* stream);
+int lasr_w2v_gather_rows(const void* src, int src_dtype, int64_t stride_b, int64_t stride_t, const int32_t* midx,
+                         int B, int T, int M, int d, void* dst, int dst_dtype, void* stream);
+int lasr_w2v_scatter_rows(const void* src, int src_dtype, const int32_t* midx, int B, int T, int M, int d,
+                          float* dst, int64_t stride_b, int64_t stride_t, int accumulate, void* stream);
+/* Gumbel vector quantizer after the weight_proj GEMM (liteasr/nets/gumbel_vector_quantizer.py:
+ * 80-109).  logits [R][G V]; per (row, group) code = argmax_v (logit + gumbel) / tau (train,
+ * :93) or argmax_v logit (hard = 1: eval, :80-85,97), ties to the smaller index; out [R][G vd] =
+ * the chosen rows of vars [G V][vd] fp32 (:106-109), codes [R][G].  noise [R G][V] fp32 overrides
+ * the counter-hash draw (seed + the registered step counter).  Backward (straight-through, the
+ * hard = True branch of F.gumbel_softmax): dlogits = y (s - <y, s>) / tau with y = softmax((logit +
+ * gumbel) / tau), s_v = <dout[row, group], vars[group, v]> (zeros when hard = 1); dvars += the
+ * row-ordered sum of dout over the rows that chose each code.  V <= 8192 in the backward. */
+int lasr_w2v_gumbel_fwd(const void* logits, int dtype, const float* noise, uint64_t seed, float tau, int hard,
+                        int64_t R, int G, int V, const float* vars, int vd, void* out, int out_dtype,
+                        int32_t* codes, void* stream);
+int lasr_w2v_gumbel_bwd(const void* logits, int dtype, const float* noise, uint64_t seed, float tau, int hard,
+                        int64_t R, int G, int V, const float* vars, int vd, const void* dout, int dout_dtype,
+                        const int32_t* codes, void* dlogits, int dlogits_dtype, float* dvars, void* stream);
+/* Contrastive head (wav2vec2.py:336-380 + nn.CrossEntropyLoss, criterions/wav2vec_loss.py:25,35)
+ * without the (N+1, B, M, D) target tensor.  x, y [B][M][D] fp32; neg [B][M N] int32 rows of
+ * y viewed [B M][D] (wav2vec2.py:348-359); codes [B M][G] from the quantizer.  logits
+ * [M B][N + 1] (row m B + b; column 0 the positive) = cosine similarity (fp32, each norm clamped
+ * at 1e-8) / logit_temp, -inf where a negative's codes equal the positive's in every group
+ * (wav2vec2.py:373-375 by code equality) or its index is out of range; lse, row_loss [B M];
+ * loss [1] = mean cross-entropy against class 0.  Backward: gout [1] (NULL = 1) scales; dx, dy
+ * [B][M][D] fp32 are overwritten; dy sums the positive's term and then every (m, n) whose
+ * index points at the row, in (m, n) order.  ws: B M (N + 1) 2 floats. */
+int lasr_w2v_contrast_fwd(const float* x, const float* y, const int32_t* neg, const int32_t* codes, int G, int B,
+                          int M, int N, int D, float logit_temp, float* logits, float* lse, float* row_loss,
+                          float* loss, void* stream);
+int lasr_w2v_contrast_bwd(const float* x, const float* y, const int32_t* neg, const int32_t* codes, int G, int B,
+                          int M, int N, int D, float logit_temp, const float* lse, const float* gout, float* dx,
+                          float* dy, float* ws, int64_t ws_floats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -224,6 +224,23 @@ SIGNATURES = {
     "lasr_rnnt_search_workspace": [_i, _i, _i, _i, _i, _i, _i],
     "lasr_rnnt_search_init": [C.POINTER(RnntSearchArgs), _i, _p],
     "lasr_rnnt_search_expand": [C.POINTER(RnntSearchArgs), _i, _p],
+    "lasr_w2v_conv0_fwd": [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p],
+    "lasr_w2v_conv0_dw_parts": [_i, _i],
+    "lasr_w2v_conv0_dw": [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _l, _p],
+    "lasr_w2v_ln_act_fwd": [_p, _i, _l, _i, _p, _p, _f, _i, _p, _i, _p, _p, _p],
+    "lasr_w2v_ln_act_bwd": [_p, _i, _p, _i, _l, _i, _p, _p, _p, _p, _i, _p, _i, _p, _p, _p, _l, _p],
+    "lasr_w2v_col2im1d": [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p],
+    "lasr_w2v_group_pack": [_p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p],
+    "lasr_w2v_group_unpack": [_p, _i, _p, _i, _p, _i, _i, _i, _i, _p, _p],
+    "lasr_w2v_group_colsum": [_p, _i, _i, _l, _i, _p, _p],
+    "lasr_w2v_mask_fwd": [_p, _p, _i, _i, _i, _i, _p, _p],
+    "lasr_w2v_mask_bwd": [_p, _p, _i, _i, _i, _i, _p, _p],
+    "lasr_w2v_gather_rows": [_p, _i, _l, _l, _p, _i, _i, _i, _i, _p, _i, _p],
+    "lasr_w2v_scatter_rows": [_p, _i, _p, _i, _i, _i, _i, _p, _l, _l, _i, _p],
+    "lasr_w2v_gumbel_fwd": [_p, _i, _p, _u, _f, _i, _l, _i, _i, _p, _i, _p, _i, _p, _p],
+    "lasr_w2v_gumbel_bwd": [_p, _i, _p, _u, _f, _i, _l, _i, _i, _p, _i, _p, _i, _p, _p, _i, _p, _p],
+    "lasr_w2v_contrast_fwd": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p],
+    "lasr_w2v_contrast_bwd": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p, _l, _p],
 }
 _RESTYPES = {"lasr_last_error": C.c_char_p, "lasr_spec_augment_ws_bytes": C.c_int64,
              "lasr_rnnt_search_workspace": C.c_int64,

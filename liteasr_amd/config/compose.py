@@ -158,10 +158,13 @@ def _defaults_entries(defaults) -> List[Tuple[Optional[str], str]]:
 def _load_group_option(config_dir: Optional[str], group: str, option: str, seen=()) -> Dict[str, Any]:
     if option == MISSING or option is None:
         raise ConfigError(f"You must specify '{group}', e.g. {group}=<option>")
-    if (group, option) in seen:
+    # a preset file named like a registered option extends that option (criterion/wav2vec.yaml over
+    # the registered "wav2vec"): its own name in its defaults list is the registered node
+    own = bool(seen) and seen[-1] == (group, option) and _registered_node(group, option) is not None
+    if (group, option) in seen and not own:
         raise ConfigError(f"cyclic defaults: {group}/{option}")
     path = os.path.join(config_dir, group, f"{option}.yaml") if config_dir else None
-    if path and os.path.exists(path):
+    if path and os.path.exists(path) and not own:
         data = _load_yaml(path)
         entries = _defaults_entries(data.pop("defaults", []))
         node: Dict[str, Any] = {}

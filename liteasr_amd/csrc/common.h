@@ -59,7 +59,7 @@ LASR_DEV void st8(bf16_t* p, const float v[8]) {
   *(uint4*)p = make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-// N consecutive elements (N in 1,2,4,8,16; pointer aligned to N elements) <-> fp32.
+// N consecutive elements (N in 1,2,4,8,12,16; pointer aligned to min(N, 4 for N = 12) elements) <-> fp32.
 template <int N>
 LASR_DEV void ldv(const float* p, float* v) {
   if constexpr (N == 1) v[0] = p[0];
@@ -82,9 +82,13 @@ LASR_DEV void ldv(const bf16_t* p, float* v) {
     const uint2 w = *(const uint2*)p;
     v[0] = __uint_as_float(w.x << 16); v[1] = __uint_as_float(w.x & 0xFFFF0000u);
     v[2] = __uint_as_float(w.y << 16); v[3] = __uint_as_float(w.y & 0xFFFF0000u);
-  } else {
+  } else if constexpr (N % 8 == 0) {
 #pragma unroll
     for (int j = 0; j < N; j += 8) ld8(p + j, v + j);
+  } else {  // N = 12 (D 768): 8-byte pieces, the alignment a lane's 24-byte run has
+    static_assert(N % 4 == 0, "ldv: N");
+#pragma unroll
+    for (int j = 0; j < N; j += 4) ldv<4>(p + j, v + j);
   }
 }
 template <int N>
@@ -102,9 +106,13 @@ LASR_DEV void stv(bf16_t* p, const float* v) {
   else if constexpr (N == 2) *(uint32_t*)p = pk_bf16(v[0], v[1]);
   else if constexpr (N == 4)
     *(uint2*)p = make_uint2(pk_bf16(v[0], v[1]), pk_bf16(v[2], v[3]));
-  else {
+  else if constexpr (N % 8 == 0) {
 #pragma unroll
     for (int j = 0; j < N; j += 8) st8(p + j, v + j);
+  } else {
+    static_assert(N % 4 == 0, "stv: N");
+#pragma unroll
+    for (int j = 0; j < N; j += 4) stv<4>(p + j, v + j);
   }
 }
 

@@ -270,6 +270,7 @@ extern "C" int lasr_layernorm_fwd(const void* x, int x_dtype, int64_t rows, int 
     case 2: ln_fwd_npl<2>(x, x_dtype, rows, gamma, beta, eps, y, y_dtype, mean, rstd, y2, y2_dtype, d2, st); break;
     case 4: ln_fwd_npl<4>(x, x_dtype, rows, gamma, beta, eps, y, y_dtype, mean, rstd, y2, y2_dtype, d2, st); break;
     case 8: ln_fwd_npl<8>(x, x_dtype, rows, gamma, beta, eps, y, y_dtype, mean, rstd, y2, y2_dtype, d2, st); break;
+    case 12: ln_fwd_npl<12>(x, x_dtype, rows, gamma, beta, eps, y, y_dtype, mean, rstd, y2, y2_dtype, d2, st); break;
     case 16: ln_fwd_npl<16>(x, x_dtype, rows, gamma, beta, eps, y, y_dtype, mean, rstd, y2, y2_dtype, d2, st); break;
     default: lasr_set_error("lasr_layernorm_fwd: D=%d unsupported", D); return LASR_ERR_INVALID;
   }
@@ -349,7 +350,7 @@ extern "C" int lasr_layernorm_bwd(const void* x, int x_dtype, const void* dy, in
   hipStream_t st = (hipStream_t)stream;
   switch (D / 64) {
 #define CASE(n) case n: ln_bwd_npl<n>(x, x_dtype, dy, dy_dtype, rows, gamma, mean, rstd, dres, dres_dtype, dx, dx_dtype, workspace, gb, gb_dtype, bscale, bd, st); break;
-    CASE(1) CASE(2) CASE(4) CASE(8) CASE(16)
+    CASE(1) CASE(2) CASE(4) CASE(8) CASE(12) CASE(16)
 #undef CASE
     default: lasr_set_error("lasr_layernorm_bwd: D=%d unsupported", D); return LASR_ERR_INVALID;
   }

@@ -1315,3 +1315,110 @@ def rnnt_search_expand(args, mode=0):
     """The launches of one expansion (LSTM layers + lin_dec + joint + finalise); mode 1
     stops after the candidates (host-loop driver)."""
     N.call("lasr_rnnt_search_expand", C.byref(args), mode, stream())
+
+
+# ------------------------------------------------------------------ wav2vec 2.0 ---
+def w2v_conv0_fwd(x, w, bias, k, s, y):
+    """Extractor layer 0 (lasr_w2v_conv0_fwd): x [B, T_in] fp32 -> y [B, T_out, C] fp32."""
+    B, Tin = x.shape
+    N.call("lasr_w2v_conv0_fwd", ptr(x), B, Tin, y.shape[2], k, s, ptr(w), ptr(bias), ptr(y), stream())
+
+
+def w2v_conv0_dw(x, dy, k, s, dw):
+    """dw [C, k] += layer 0's weight gradient, fixed order (lasr_w2v_conv0_dw)."""
+    B, Tin = x.shape
+    Cc = dy.shape[2]
+    ws = WS.get(N.load().lasr_w2v_conv0_dw_parts(B, dy.shape[1]) * Cc * k, x.device)
+    N.call("lasr_w2v_conv0_dw", ptr(x), ptr(dy), dt(dy), B, Tin, Cc, k, s, ptr(dw), ptr(ws), ws.numel(), stream())
+
+
+def w2v_ln_act_fwd(x, gamma, beta, eps, act, y, mean, rstd):
+    """y = act(LayerNorm(x)) over the last dim, fp32 statistics; act 1 = exact GELU."""
+    Cc = x.shape[-1]
+    N.call("lasr_w2v_ln_act_fwd", ptr(x), dt(x), x.numel() // Cc, Cc, ptr(gamma), ptr(beta), float(eps), int(act),
+           ptr(y), dt(y), ptr(mean), ptr(rstd), stream())
+
+
+def w2v_ln_act_bwd(x, dy, gamma, beta, mean, rstd, act, dx, dgamma, dbeta):
+    Cc = x.shape[-1]
+    rows = x.numel() // Cc
+    ws = WS.get((rows + 63) // 64 * 2 * Cc, x.device)
+    N.call("lasr_w2v_ln_act_bwd", ptr(x), dt(x), ptr(dy), dt(dy), rows, Cc, ptr(gamma), ptr(beta), ptr(mean),
+           ptr(rstd), int(act), ptr(dx), dt(dx), ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel(), stream())
+
+
+def w2v_col2im1d(dcol, Tin, Cc, k, s, dx):
+    B, Tout = dcol.shape[0], dcol.shape[1]
+    N.call("lasr_w2v_col2im1d", ptr(dcol), dt(dcol), B, Tin, Tout, Cc, k, s, ptr(dx), stream())
+
+
+def w2v_group_pack(src, G, front, dst, yg=None, bias=None):
+    """dst [G, B, Tp, cg] <- src [B, T, G cg] fp32 at rows front.., zeros elsewhere (x GELU'(yg + bias))."""
+    B, T, d = src.shape
+    N.call("lasr_w2v_group_pack", ptr(src), B, T, G, d // G, front, dst.shape[2], ptr(yg),
+           dt(yg) if yg is not None else 0, ptr(bias), ptr(dst), dt(dst), stream())
+
+
+def w2v_group_unpack(yg, bias, act, res, out):
+    G, B, T, cg = yg.shape
+    N.call("lasr_w2v_group_unpack", ptr(yg), dt(yg), ptr(bias), int(act), ptr(res), B, T, G, cg, ptr(out), stream())
+
+
+def w2v_group_colsum(x, out):
+    G, cg = x.shape[0], x.shape[-1]
+    N.call("lasr_w2v_group_colsum", ptr(x), dt(x), G, x.numel() // (G * cg), cg, ptr(out), stream())
+
+
+def w2v_mask_fwd(x, midx, emb):
+    B, T, d = x.shape
+    N.call("lasr_w2v_mask_fwd", ptr(x), ptr(midx), B, T, midx.shape[1], d, ptr(emb), stream())
+
+
+def w2v_mask_bwd(dx, midx, demb):
+    B, T, d = dx.shape
+    N.call("lasr_w2v_mask_bwd", ptr(dx), ptr(midx), B, T, midx.shape[1], d, ptr(demb), stream())
+
+
+def w2v_gather_rows(src, midx, dst, time_major=False):
+    """dst [B, M, d] = rows midx of src ([B, T, d], or [T, B, d] when time_major)."""
+    d = src.shape[2]
+    B, T = (src.shape[1], src.shape[0]) if time_major else (src.shape[0], src.shape[1])
+    sb, st = (d, B * d) if time_major else (T * d, d)
+    N.call("lasr_w2v_gather_rows", ptr(src), dt(src), sb, st, ptr(midx), B, T, midx.shape[1], d, ptr(dst), dt(dst),
+           stream())
+
+
+def w2v_scatter_rows(src, midx, dst, time_major=False, accumulate=False):
+    d = dst.shape[2]
+    B, T = (dst.shape[1], dst.shape[0]) if time_major else (dst.shape[0], dst.shape[1])
+    sb, st = (d, B * d) if time_major else (T * d, d)
+    N.call("lasr_w2v_scatter_rows", ptr(src), dt(src), ptr(midx), B, T, midx.shape[1], d, ptr(dst), sb, st,
+           int(accumulate), stream())
+
+
+def w2v_gumbel_fwd(logits, G, vars_, tau, hard, out, codes, noise=None, seed=0):
+    R = logits.shape[0]
+    V = logits.shape[1] // G
+    N.call("lasr_w2v_gumbel_fwd", ptr(logits), dt(logits), ptr(noise), seed, float(tau), int(hard), R, G, V,
+           ptr(vars_), vars_.shape[-1], ptr(out), dt(out), ptr(codes), stream())
+
+
+def w2v_gumbel_bwd(logits, G, vars_, tau, hard, dout, codes, dlogits, dvars, noise=None, seed=0):
+    R = logits.shape[0]
+    V = logits.shape[1] // G
+    N.call("lasr_w2v_gumbel_bwd", ptr(logits), dt(logits), ptr(noise), seed, float(tau), int(hard), R, G, V,
+           ptr(vars_), vars_.shape[-1], ptr(dout), dt(dout), ptr(codes), ptr(dlogits), dt(dlogits), ptr(dvars),
+           stream())
+
+
+def w2v_contrast_fwd(x, y, neg, codes, Nneg, temp, logits, lse, row_loss, loss):
+    B, M, D = x.shape
+    N.call("lasr_w2v_contrast_fwd", ptr(x), ptr(y), ptr(neg), ptr(codes), codes.shape[-1], B, M, Nneg, D,
+           float(temp), ptr(logits), ptr(lse), ptr(row_loss), ptr(loss), stream())
+
+
+def w2v_contrast_bwd(x, y, neg, codes, Nneg, temp, lse, gout, dx, dy):
+    B, M, D = x.shape
+    ws = torch.empty(B * M * (Nneg + 1) * 2, dtype=torch.float32, device=x.device)
+    N.call("lasr_w2v_contrast_bwd", ptr(x), ptr(y), ptr(neg), ptr(codes), codes.shape[-1], B, M, Nneg, D,
+           float(temp), ptr(lse), ptr(gout), ptr(dx), ptr(dy), ptr(ws), ws.numel(), stream())

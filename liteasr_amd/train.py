@@ -69,8 +69,26 @@ def train(cfg):
     build_trainer(cfg).run()
 
 
+def group_options():
+    """{group: options} a command line can name: the registered classes and the preset files
+    (what Hydra's --help prints as "Configuration groups")."""
+    from .config.compose import PRESET_DIR, _registries
+
+    out = {}
+    for group, reg in _registries().items():
+        names = set(reg)
+        gdir = os.path.join(PRESET_DIR, group)
+        if os.path.isdir(gdir):
+            names |= {f[:-5] for f in os.listdir(gdir) if f.endswith(".yaml")}
+        out[group] = sorted(names)
+    return out
+
+
 def parse_args(argv=None):
-    p = argparse.ArgumentParser(prog="liteasr_amd.train", description=__doc__.splitlines()[0])
+    groups = "\n".join(f"  {g}: {', '.join(o)}" for g, o in group_options().items())
+    p = argparse.ArgumentParser(prog="liteasr_amd.train", description=__doc__.splitlines()[0],
+                                epilog="configuration groups (group=option):\n" + groups,
+                                formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--config-dir", "-cd", default=None, help="directory with <config-name>.yaml and group dirs")
     p.add_argument("--config-name", "-cn", default="config")
     p.add_argument("--cfg", choices=["job", "hydra", "all"], default=None,
