@@ -34,6 +34,9 @@ build/obj/%.o: liteasr_amd/csrc/%.hip $(HDRS)
 	@mkdir -p build/obj
 	$(HIPCC) $(FLAGS) -c $< -o $@
 
+# the device-side CTC prefix search repeats the host search's double arithmetic: same rule
+build/obj/rescore.o: FLAGS += -ffp-contract=off
+
 $(LIB): $(OBJ)
 	@mkdir -p liteasr_amd/lib
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^

@@ -750,6 +750,44 @@ int64_t lasr_rnnt_search_workspace(int Tcap, int layers, int H, int J, int V, in
 int lasr_rnnt_search_init(const lasr_rnnt_search_args* a, int Tp, void* stream);
 int lasr_rnnt_search_expand(const lasr_rnnt_search_args* a, int mode, void* stream);
 
+/* ---- Attention rescoring on the device (liteasr/models/u2.py:218-317, csrc/rescore.hip) ----
+ * The part of U2.inference between the encoder and the answer, for one utterance and the
+ * reference's beam of 10, as three graph-capturable entries around the decoder pass:
+ *
+ * lasr_rescore_search: CTC prefix beam search (u2.py:218-263) over topk_val / topk_idx
+ *   [>= T', k] (k = min(10, V), what lasr_logsoftmax_topk wrote); T' = Tp_dev[0] is read on
+ *   the device (clamped to [0, Tcap]).  Double arithmetic and the semantics of
+ *   lasr_ctc_prefix_beam_search (liteasr_decode.h) step for step; prefixes are compared
+ *   exactly (a table keyed by (parent prefix, token), never by a fingerprint).
+ * lasr_rescore_prep: the decoder inputs of the n-best at the static shape, L1cap = Lcap + 1:
+ *   ys_in int32 [10][L1cap] (sos, the tokens, eos padding), dec_mask u8 [10][L1cap][dec_ld]
+ *   (1 = masked: key >= len + 1, key > query, or a padding column >= L1cap), gather_idx int32
+ *   [10 L1cap] (the tokens, eos at position len, then -1; all -1 for rows >= n), mem_mask u8
+ *   [10][Tcap] (1 at frames >= T').
+ * lasr_rescore_pick: gathered [10][L1cap] = attention log-probs at gather_idx; per hypothesis
+ *   the float32 running sum over positions 0..len, plus float32(score * ctc_weight); the first
+ *   strict maximum wins (u2.py:300-315).
+ *
+ * arena: 256-B aligned, lasr_rescore_workspace(Tcap, Lcap) bytes.  It starts with the result
+ * block (int32 words), which is all the host reads back:
+ *   [0] error bits (1: a kept hypothesis is longer than Lcap; 2: prefix table full; 4: a frame
+ *       without k candidates), [1] n (1..10), [2] best index, [3] its length, [4] T',
+ *   [8..18) lengths, [20..40) scores (10 doubles), [40..50) rescoring totals (10 floats),
+ *   [64, 64 + Lcap) the best hypothesis' tokens, then tokens [10][Lcap], then a copy of
+ *   gathered [10][L1cap];
+ * then, from the next multiple of 256 B, the prefix table: cap x uint64 keys (parent slot << 32
+ * | token, all ones = empty), cap = the power of two >= max(1024, 2 (100 Tcap + 1)).
+ * With error bit 1 the lengths are still the true ones; such hypotheses carry no tokens and
+ * count as empty in prep, and pick leaves the best index at 0. */
+int64_t lasr_rescore_workspace(int Tcap, int Lcap);
+int lasr_rescore_search(void* arena, int64_t arena_bytes, int Tcap, int Lcap, int k, int blank, int beam,
+                        const float* topk_val, const int32_t* topk_idx, const int32_t* Tp_dev, void* stream);
+int lasr_rescore_prep(const void* arena, int64_t arena_bytes, int Tcap, int Lcap, int sos, int eos,
+                      int32_t* ys_in, uint8_t* dec_mask, int dec_ld, int32_t* gather_idx, uint8_t* mem_mask,
+                      void* stream);
+int lasr_rescore_pick(void* arena, int64_t arena_bytes, int Tcap, int Lcap, const float* gathered,
+                      double ctc_weight, void* stream);
+
 /* ---- wav2vec 2.0 pretraining (csrc/w2v.hip) -----------------------------------------
  * Activations are channels-last: [B][T][C].  `dtype` arguments are LASR_F32 / LASR_BF16.
  * Every parameter-gradient output ACCUMULATES (+=) in a fixed summation order; no entry

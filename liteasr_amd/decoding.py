@@ -206,8 +206,184 @@ def attention_beam_search(model, x, beam=10, trace=None):
     return hyps[best].tolist()
 
 
+_BEAM = 10  # the reference's beam (u2.py:160-317, transducer.py:137): the only one the device searches build
+
+# ============================================== attention rescoring on the device ===
+def attention_rescore_host(model, x, ctc_weight=0.5, encoder_graph=True):
+    """u2.py:269-317 through the host: top-k copied down, native prefix search, the n-best
+    padded in Python, an eager decoder pass at the utterance's shapes, the gathers copied down.
+    This is what U2.inference runs (the device-resident pass below beats it only at T = 400,
+    not at T = 1000).  encoder_graph=False: the same steps after an eager encoder
+    pass."""
+    if encoder_graph:
+        hyps, h, T = ctc_prefix_beam_search_nbest(model, x, beam=10)
+    else:
+        h, T = encode(model, x, graph=False)
+        logits = FN.ctc_logits(h, model)
+        vals, idx, _ = K.logsoftmax_topk(logits, min(10, logits.shape[1]))
+        hyps = prefix_beam_search(vals.cpu().numpy(), idx.cpu().numpy(), 10, model.blank)
+    return tuple(hyps[rescore(model, hyps, h, T, ctc_weight=ctc_weight)][0])
+
+
+# result block words of the rescoring arena (include/liteasr_hip.h)
+_R_ERR, _R_N, _R_BEST, _R_BESTLEN, _R_TP, _R_LENS, _R_SCORE, _R_TOTAL, _R_HEAD = 0, 1, 2, 3, 4, 8, 20, 40, 64
+_RESCORE_ERRORS = {2: "prefix table full", 4: "a frame without k finite candidates"}
+_CTC_WEIGHT = 0.5  # u2.py:269
+
+
+def rescore_layout(Tcap, Lcap):
+    """Word offsets of the result block's variable part: best tokens, tokens [10, Lcap], the
+    copy of the gathered log-probs [10, Lcap + 1]; head_words = the words the host reads."""
+    best = _R_HEAD
+    toks = best + Lcap
+    gath = toks + _BEAM * Lcap
+    return {"best": best, "toks": toks, "gath": gath, "head_words": gath + _BEAM * (Lcap + 1)}
+
+
+class _Rescore:
+    """Arena, static buffers and the captured graph of one model at one (Tcap, Lcap)."""
+
+    def __init__(self, model, Tcap, Lcap, d, adt, dev):
+        self.Tcap, self.Lcap, self.L1 = Tcap, Lcap, Lcap + 1
+        self.k = min(_BEAM, model.vocab_size)
+        self.off = rescore_layout(Tcap, Lcap)
+        self.arena = torch.zeros(K.rescore_workspace(Tcap, Lcap), dtype=torch.uint8, device=dev)
+        self.mem = torch.zeros(Tcap, d, dtype=adt, device=dev)  # rows >= T' stay zero
+        self.tp = torch.zeros(1, dtype=torch.int32, device=dev)
+        L1 = self.L1
+        self.ys_in = torch.zeros(_BEAM, L1, dtype=torch.int32, device=dev)
+        # 16-B aligned mask rows, as _prep allocates them (the attention kernels stage tiles by LDS-DMA)
+        self.dec_mask = torch.ones(_BEAM, L1, (L1 + 15) // 16 * 16, dtype=torch.uint8, device=dev)[:, :, :L1]
+        self.gidx = torch.full((_BEAM * L1,), -1, dtype=torch.int32, device=dev)
+        self.mem_mask = torch.ones(_BEAM, Tcap, dtype=torch.uint8, device=dev)
+        self.filled = 0
+        self.graph = None
+        self.keep = None
+
+    def launches(self, model):
+        """ctc_lo + log-softmax top-k over all Tcap rows, the search (T' on the device), the
+        decoder inputs, the decoder at (10, L1cap, Tcap) under the memory mask, the gather, the
+        pick: one stream, in this order."""
+        Tcap, Lcap, L1 = self.Tcap, self.Lcap, self.L1
+        logits = FN.ctc_logits(self.mem, model)
+        vals, idx, _ = K.logsoftmax_topk(logits, self.k)
+        K.rescore_search(self.arena, Tcap, Lcap, vals, idx, self.tp, model.blank, _BEAM)
+        K.rescore_prep(self.arena, Tcap, Lcap, model.sos, model.eos, self.ys_in, self.dec_mask, self.gidx,
+                       self.mem_mask)
+        d = self.mem.shape[1]
+        mem = self.mem.view(1, Tcap, d).expand(_BEAM, Tcap, d).reshape(_BEAM * Tcap, d)
+        h_attn = FN.decoder_logits(model, mem, self.ys_in, self.dec_mask, self.mem_mask, _BEAM, L1, Tcap)
+        _, _, g = K.logsoftmax_topk(h_attn, 0, gather_idx=self.gidx)
+        K.rescore_pick(self.arena, Tcap, Lcap, g, _CTC_WEIGHT)
+        return vals, idx, g
+
+    def capture(self, model):
+        cur = torch.cuda.current_stream()
+        side = torch.cuda.Stream()
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):  # warm-up: workspaces, working copies, allocator pools
+            self.launches(model)
+        cur.wait_stream(side)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self.keep = self.launches(model)
+        self.graph = g
+        self.ws = K.WS.buf.get(self.arena.device.index)  # the workspace the graph was captured against
+
+    def run(self, model, h, Tp):
+        """One utterance: memory rows and T' in, one replay, the result block out (ONE copy)."""
+        if self.graph is None:
+            self.capture(model)
+        self.mem[:Tp].copy_(h[:Tp])
+        if self.filled > Tp:
+            self.mem[Tp:self.filled].zero_()
+        self.filled = Tp
+        self.tp.fill_(Tp)
+        self.graph.replay()
+        return self.arena[: 4 * self.off["head_words"]].cpu().numpy().view(np.int32)
+
+
+def _rescore_state(model, Tcap, Lcap, h):
+    st = model.store
+    ver = (st.flat._version, st.generation, h.dtype, h.shape[1])
+    cache = model.__dict__.setdefault("_rescore_states", {})
+    if cache.get("ver") != ver:  # a weight update: the working copies a graph reads may be stale
+        cache.clear()
+        cache["ver"] = ver
+        cache["lcap"] = {}
+    if Lcap is None:
+        return cache["lcap"]
+    s = cache.get((Tcap, Lcap))
+    if s is None:
+        s = cache[(Tcap, Lcap)] = _Rescore(model, Tcap, Lcap, h.shape[1], h.dtype, h.device)
+    return s
+
+
+def rescore_nbest(head, Lcap):
+    """[(tokens, score)] of a result block (int32 words)."""
+    off = rescore_layout(0, Lcap)
+    n = int(head[_R_N])
+    lens = head[_R_LENS:_R_LENS + _BEAM]
+    score = head[_R_SCORE:_R_SCORE + 2 * _BEAM].view(np.float64)
+    toks = head[off["toks"]:off["toks"] + _BEAM * Lcap].reshape(_BEAM, Lcap)
+    return [(toks[i, :lens[i]].tolist(), float(score[i])) for i in range(n)]
+
+
+def attention_rescore_device(model, x, trace=None, encoder_graph=True):
+    """u2.py:269-317 (beam 10, ctc weight 0.5) for one utterance x [1, T, F] with everything
+    after the encoder on the device: the encoder output goes into a static memory buffer
+    [Tcap, d] (rows >= T' zero), T' into a device word, and ONE replay of a captured linear
+    hipGraph runs ctc_lo, the per-frame log-softmax top-k, the CTC prefix beam search
+    (csrc/rescore.hip), the decoder inputs, the decoder at the static shape (10, Lcap + 1,
+    Tcap) under the memory mask, the gather and the pick; ONE device-to-host copy brings back
+    the result block.  Tcap = the power of two >= max(T', 64); Lcap starts at 64 and doubles
+    (the utterance is run again) when a kept hypothesis is longer; a Tcap bucket then keeps the
+    largest Lcap it has needed.  States, and so graphs, are
+    cached per (Tcap, Lcap) and dropped on a weight update.  trace (a dict) receives "nbest"
+    [(tokens, score)], "gathered" [n, Lmax + 1], "best" and "totals"."""
+    if x.device.type != "cuda":
+        raise RuntimeError("liteasr_amd decoding runs on the HIP device only")
+    if x.dim() != 3 or x.shape[0] != 1:
+        raise ValueError("attention_rescore_device: one utterance x [1, T, F]")
+    h, Tp = encode(model, x, graph=encoder_graph)
+    if Tp <= 0:
+        raise ValueError(f"attention_rescore_device: {x.shape[1]} frames subsample to none")
+    Tcap = 64
+    while Tcap < Tp:
+        Tcap *= 2
+    # a bucket starts at Lcap 64 and keeps the largest Lcap it has needed: after an overflow,
+    # later utterances of the bucket are not run again from 64
+    hint = _rescore_state(model, Tcap, None, h)
+    Lcap = hint.get(Tcap, 64)
+    while True:
+        s = _rescore_state(model, Tcap, Lcap, h)
+        head = s.run(model, h, Tp)
+        err = int(head[_R_ERR])
+        if err & ~1:
+            raise RuntimeError("attention_rescore_device: " + _RESCORE_ERRORS.get(err & ~1, f"error {err}"))
+        if not err:
+            break
+        if Lcap >= Tcap:
+            raise RuntimeError(f"attention_rescore_device: hypothesis longer than T' cap {Tcap}")
+        Lcap *= 2
+    hint[Tcap] = Lcap
+    assert int(head[_R_TP]) == Tp, (int(head[_R_TP]), Tp)
+    n, best, blen = int(head[_R_N]), int(head[_R_BEST]), int(head[_R_BESTLEN])
+    off = s.off
+    if trace is not None:
+        hyps = rescore_nbest(head, Lcap)
+        Lmax = max(1, max(len(t) for t, _ in hyps))
+        g = head[off["gath"]:off["gath"] + _BEAM * (Lcap + 1)].view(np.float32).reshape(_BEAM, Lcap + 1)
+        trace["nbest"] = hyps
+        trace["gathered"] = g[:n, :Lmax + 1].copy()
+        trace["best"] = best
+        trace["totals"] = head[_R_TOTAL:_R_TOTAL + n].view(np.float32).copy()
+        trace["caps"] = (Tcap, Lcap)
+    return tuple(head[off["best"]:off["best"] + blen].tolist())
+
+
 # ======================================================= transducer beam search ===
-_BEAM = 10
 _ERRORS = {1: "node arena full", 2: "state-slot arena full", 3: "trie hash full", 4: "non-finite joint logits",
            5: "empty hypothesis list"}
 # ctrl words of the search arena (include/liteasr_hip.h)

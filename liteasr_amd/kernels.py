@@ -1317,6 +1317,64 @@ def rnnt_search_expand(args, mode=0):
     N.call("lasr_rnnt_search_expand", C.byref(args), mode, stream())
 
 
+# ----------------------------------------------- attention rescoring on the device ---
+def rescore_workspace(Tcap, Lcap):
+    """Arena bytes of the device-resident rescoring (lasr_rescore_workspace)."""
+    return int(N.load().lasr_rescore_workspace(int(Tcap), int(Lcap)))
+
+
+def _rescore_arena(arena, Tcap, Lcap, who, *others):
+    """The arena's size, and that it and every other tensor handed to the kernel live on one HIP
+    device (the kernels take raw pointers)."""
+    if arena.dtype != torch.uint8 or not arena.is_contiguous() or arena.numel() < rescore_workspace(Tcap, Lcap):
+        raise ValueError(f"{who}: arena must be contiguous uint8 of rescore_workspace(Tcap, Lcap) bytes")
+    if not arena.is_cuda or any(t.device != arena.device for t in others):
+        raise ValueError(f"{who}: the arena and every tensor must be on the same HIP device")
+
+
+def rescore_search(arena, Tcap, Lcap, vals, idx, tp_dev, blank, beam=10):
+    """CTC prefix beam search over the candidates vals / idx [>= Tcap, k] (lasr_rescore_search);
+    tp_dev: int32 device word holding T'.  The result block at the head of the arena receives
+    n, the lengths, double scores and tokens."""
+    _rescore_arena(arena, Tcap, Lcap, "rescore_search", vals, idx, tp_dev)
+    if vals.dtype != torch.float32 or idx.dtype != torch.int32 or vals.shape != idx.shape or vals.dim() != 2 \
+            or not vals.is_contiguous() or not idx.is_contiguous():
+        raise ValueError("rescore_search: vals f32 / idx i32, contiguous [rows, k]")
+    if vals.shape[0] < Tcap:
+        raise ValueError(f"rescore_search: {vals.shape[0]} candidate rows < Tcap = {Tcap}")
+    if tp_dev.dtype != torch.int32 or tp_dev.numel() < 1:
+        raise ValueError("rescore_search: tp_dev must be an int32 device word")
+    N.call("lasr_rescore_search", ptr(arena), arena.numel(), Tcap, Lcap, vals.shape[1], int(blank), int(beam),
+           ptr(vals), ptr(idx), ptr(tp_dev), stream())
+
+
+def rescore_prep(arena, Tcap, Lcap, sos, eos, ys_in, dec_mask, gather_idx, mem_mask):
+    """Decoder inputs of the n-best in the arena (lasr_rescore_prep): ys_in i32 [10, L1cap],
+    dec_mask u8 [10, L1cap, >= L1cap] (row stride = its stride(1)), gather_idx i32 [10 L1cap],
+    mem_mask u8 [10, Tcap]."""
+    _rescore_arena(arena, Tcap, Lcap, "rescore_prep", ys_in, dec_mask, gather_idx, mem_mask)
+    L1 = Lcap + 1
+    ld = dec_mask.stride(1)
+    if (ys_in.dtype != torch.int32 or tuple(ys_in.shape) != (10, L1) or not ys_in.is_contiguous()
+            or gather_idx.dtype != torch.int32 or gather_idx.numel() != 10 * L1 or not gather_idx.is_contiguous()
+            or mem_mask.dtype != torch.uint8 or tuple(mem_mask.shape) != (10, Tcap) or not mem_mask.is_contiguous()
+            or dec_mask.dtype != torch.uint8 or tuple(dec_mask.shape[:2]) != (10, L1) or dec_mask.shape[2] < L1
+            or dec_mask.stride(2) != 1 or dec_mask.stride(0) != L1 * ld or ld < L1):
+        raise ValueError("rescore_prep: output shapes / dtypes")
+    if (10 * L1 - 1) * ld + ld > dec_mask.untyped_storage().nbytes() - dec_mask.storage_offset():
+        raise ValueError("rescore_prep: dec_mask rows walk past its storage")
+    N.call("lasr_rescore_prep", ptr(arena), arena.numel(), Tcap, Lcap, int(sos), int(eos), ptr(ys_in), ptr(dec_mask),
+           ld, ptr(gather_idx), ptr(mem_mask), stream())
+
+
+def rescore_pick(arena, Tcap, Lcap, gathered, ctc_weight):
+    """Best hypothesis from the gathered attention log-probs f32 [10 L1cap] (lasr_rescore_pick)."""
+    _rescore_arena(arena, Tcap, Lcap, "rescore_pick", gathered)
+    if gathered.dtype != torch.float32 or gathered.numel() != 10 * (Lcap + 1) or not gathered.is_contiguous():
+        raise ValueError("rescore_pick: gathered must be contiguous f32 [10 (Lcap + 1)]")
+    N.call("lasr_rescore_pick", ptr(arena), arena.numel(), Tcap, Lcap, ptr(gathered), float(ctc_weight), stream())
+
+
 # ------------------------------------------------------------------ wav2vec 2.0 ---
 def w2v_conv0_fwd(x, w, bias, k, s, y):
     """Extractor layer 0 (lasr_w2v_conv0_fwd): x [B, T_in] fp32 -> y [B, T_out, C] fp32."""

@@ -141,9 +141,10 @@ class U2(FusedEncoderModel):
         return self._prep(xs, xlens, ys, ylens)
 
     @torch.no_grad()
-    def inference(self, x):
-        """liteasr/models/u2.py:160-161."""
-        return self.attention_rescore(x)
+    def inference(self, x, encoder_graph=True):
+        """liteasr/models/u2.py:160-161.  encoder_graph=False runs the encoder eagerly (a frame
+        count that will not come again is not worth a graph capture)."""
+        return self.attention_rescore(x, encoder_graph=encoder_graph)
 
     @torch.no_grad()
     def attention(self, x):
@@ -163,10 +164,11 @@ class U2(FusedEncoderModel):
         return tuple(hyps[0][0])
 
     @torch.no_grad()
-    def attention_rescore(self, x):
-        """liteasr/models/u2.py:269-317 (ctc weight 0.5)."""
-        hyps, h, T = D.ctc_prefix_beam_search_nbest(self, x, beam=10)
-        return tuple(hyps[D.rescore(self, hyps, h, T, ctc_weight=0.5)][0])
+    def attention_rescore(self, x, encoder_graph=True):
+        """liteasr/models/u2.py:269-317 (ctc weight 0.5), through the host's native prefix search.
+        decoding.attention_rescore_device is the same search kept on the device; it returns the
+        same answers but beats this path only at the shorter measured length: not the default."""
+        return D.attention_rescore_host(self, x, ctc_weight=0.5, encoder_graph=encoder_graph)
 
     @classmethod
     def build_model(cls, cfg: U2Config, task=None):

@@ -1,5 +1,6 @@
 """ASR task (liteasr/tasks/asr.py:23-98): vocabulary, feature datasets, model saving."""
 
+import inspect
 import logging
 import os
 from dataclasses import dataclass, field
@@ -53,8 +54,14 @@ class ASRTask(LiteasrTask):
         else:
             raise TypeError("data_dir with type {} cannot be parsed".format(type(data_dir)))
 
-    def inference(self, x, model):
-        tokens = self.vocab.lookupi(model.inference(x), convert=True)
+    def inference(self, x, model, encoder_graph=None):
+        """encoder_graph (None: the model's default) is handed to models whose ``inference``
+        takes it: whether this utterance's frame count is worth an encoder graph capture."""
+        if encoder_graph is None or "encoder_graph" not in inspect.signature(model.inference).parameters:
+            ids = model.inference(x)
+        else:
+            ids = model.inference(x, encoder_graph=bool(encoder_graph))
+        tokens = self.vocab.lookupi(ids, convert=True)
         return "".join(tokens) if self.cfg.delimiter is None else self.cfg.delimiter.join(tokens)
 
     def save_model(self, model_name: str, model):

@@ -84,9 +84,9 @@ def group_options():
     return out
 
 
-def parse_args(argv=None):
+def parse_args(argv=None, prog="liteasr_amd.train", description=None):
     groups = "\n".join(f"  {g}: {', '.join(o)}" for g, o in group_options().items())
-    p = argparse.ArgumentParser(prog="liteasr_amd.train", description=__doc__.splitlines()[0],
+    p = argparse.ArgumentParser(prog=prog, description=description or __doc__.splitlines()[0],
                                 epilog="configuration groups (group=option):\n" + groups,
                                 formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--config-dir", "-cd", default=None, help="directory with <config-name>.yaml and group dirs")
@@ -97,16 +97,22 @@ def parse_args(argv=None):
     return p.parse_args(argv)
 
 
-def prepare(argv=None, job_name="train"):
-    """Compose + the Hydra run-dir side effects; returns (job config, run dir)."""
-    args = parse_args(argv)
+def _training_needs(key):
+    return key.split(".")[0] in ("task", "dataset", "optimization", "common")
+
+
+def prepare(argv=None, job_name="train", description=None, mandatory=_training_needs):
+    """Compose + the Hydra run-dir side effects; returns (job config, run dir).  mandatory(key)
+    says which unset (``???``) keys stop the job: Hydra complains about a missing value only
+    when it is read, so each job names what it reads."""
+    args = parse_args(argv, prog=f"liteasr_amd.{job_name}", description=description)
     cfg = compose(args.config_dir, args.config_name, args.overrides, job_name=job_name)
     if args.cfg:
         shown = cfg if args.cfg == "all" else (Node.wrap({"hydra": cfg.hydra}) if args.cfg == "hydra" else
                                                Node.wrap({k: v for k, v in cfg.items() if k != "hydra"}))
         sys.stdout.write(shown.to_yaml())
         return None, None
-    unset = [k for k in missing_keys(cfg) if k.split(".")[0] in ("task", "dataset", "optimization", "common")]
+    unset = [k for k in missing_keys(cfg) if mandatory(k)]
     if unset:
         raise ConfigError("missing mandatory value(s): " + ", ".join(unset))
     run_dir = os.path.abspath(os.path.join(cfg.hydra.runtime.cwd, str(cfg.hydra.run.dir)))
