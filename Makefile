@@ -13,11 +13,12 @@ FLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC
 
 all: $(LIB) $(IOLIB) $(DECLIB) $(COMMLIB)
 
-# host-only native feature reader (no device code); -ffp-contract=off keeps the decode
-# arithmetic bit-identical to the reference's numpy float32 expressions
-$(IOLIB): liteasr_amd/csrc/io/ark_io.cpp include/liteasr_io.h
+# host-only native feature and waveform readers (no device code); -ffp-contract=off keeps the
+# decode arithmetic bit-identical to the reference's numpy float32 expressions
+IOSRC := liteasr_amd/csrc/io/ark_io.cpp liteasr_amd/csrc/io/wav_io.cpp
+$(IOLIB): $(IOSRC) liteasr_amd/csrc/io/io_error.h include/liteasr_io.h
 	@mkdir -p liteasr_amd/lib
-	$(CXX) -O2 -std=c++17 -fPIC -shared -ffp-contract=off -pthread -o $@ $<
+	$(CXX) -O2 -std=c++17 -fPIC -shared -ffp-contract=off -pthread -o $@ $(IOSRC)
 
 # host-only CTC prefix beam search (inference); same fp-contract rule, so its double
 # arithmetic matches the reference's Python floats

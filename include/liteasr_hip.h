@@ -640,6 +640,12 @@ int lasr_u2_prep_chunk(const int64_t* xlens, const int64_t* ys, const int64_t* y
                        uint8_t* chunk_mask, int chunk_ld, int32_t* pred_len, int32_t* ylen32,
                        void* stream);
 
+/* 16-bit PCM to the fp32 waveform of the wav2vec 2.0 models: out[i] = pcm[i] * 2^-15 (exact;
+ * what soundfile.read gives for PCM_16, liteasr/dataclass/audio_data.py:31-32, as float32).
+ * The pretraining batch is copied to HBM as int16 and converted here.  pcm needs 2-byte and
+ * out 4-byte alignment only; n elements, one launch. */
+int lasr_pcm_to_float(const int16_t* pcm, int64_t n, float* out, void* stream);
+
 /* ------------------------------------------------------------------------
  * SpecAugment (liteasr/utils/transform/spec_augment.py:14-125; applied per utterance in
  * the reference's DataLoader workers, liteasr/dataset/asr_dataset.py:118).  Replaces the

@@ -58,6 +58,36 @@ int lasr_ark_read(const char* path, int64_t offset, int big_endian, void* out, i
 int lasr_ark_read_padded(int n, const char* const* paths, const int64_t* offsets, int big_endian,
                          float* out, int64_t tmax, int64_t feat_dim, int64_t* lens, int nthreads);
 
+/* ------------------------------------------------------------------------
+ * RIFF/WAVE reader of the pretraining path (wav.scp data directories).
+ *
+ * Replaces (reference, Python):
+ *   liteasr/dataclass/sheet.py:89            sf.read(wavfd) for the length -> lasr_wav_probe
+ *   liteasr/dataclass/audio_data.py:30-33    sf.read + slice               -> lasr_wav_read_i16
+ *   liteasr/dataset/pretrain_dataset.py:51-56 collator: crop + pad_sequence -> lasr_wav_read_batch
+ *
+ * Only 16-bit mono PCM is accepted: fmt tag 1, or 0xFFFE (extensible) with the PCM sub-format.
+ * Chunks before "data" are skipped in any order (odd sizes with their pad byte); a data size of
+ * 0 or 0xFFFFFFFF means "to the end of the file"; a data size beyond the file is clipped to it.
+ * Any other file is an error whose text names the file and the reason.  Samples are returned as
+ * stored (int16); sample / 32768 is what soundfile.read gives for PCM_16.
+ */
+
+/* Format of the file and where its samples are: frames = samples of the one channel,
+ * data_offset = byte position of sample 0.  Any output pointer may be NULL. */
+int lasr_wav_probe(const char* path, int* rate, int* channels, int* bits, int64_t* frames,
+                   int64_t* data_offset);
+
+/* Samples [start, start + count) into out[count]; what lies past the end of the data is
+ * zero-filled and *got (may be NULL) receives how many samples were really there. */
+int lasr_wav_read_i16(const char* path, int64_t start, int64_t count, int16_t* out, int64_t* got);
+
+/* The same window [starts[i], starts[i] + count) of each of n files into out[n][count] (which
+ * may be pinned memory), got[i] as above.  Reads run on nthreads host threads (<= 0: one per
+ * hardware thread; at most 16 either way). */
+int lasr_wav_read_batch(int n, const char* const* paths, const int64_t* starts, int64_t count,
+                        int16_t* out, int64_t* got, int nthreads);
+
 #ifdef __cplusplus
 }
 #endif

@@ -213,6 +213,7 @@ SIGNATURES = {
     "lasr_gemm_ln_bwd": [C.POINTER(GemmArgs), _p, _i, _p, _p, _p, _p, _i, _p, _i, _p, _l, _p, _i, _f, _f, _u, _p],
     "lasr_u2_prep_chunk": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _u, _i,
                            _p, _p, _p, _p, _i, _p, _p, _i, _p, _p, _p],
+    "lasr_pcm_to_float": [_p, _l, _p, _p],
     "lasr_sumsq_nparts": [_l],
     "lasr_sumsq_partial": [_p, _l, _p, _l, _p],
     "lasr_adam_step": [_p, _p, _i, _p, _p, _p, _l, _p, _i, _p, _f, _i, _f, _f, _f, _f, _f, _f,

@@ -10,6 +10,7 @@
 // Decoding arithmetic is float32 in exactly the order numpy evaluates the reference's
 // expressions (no contraction: built with -ffp-contract=off), so values are bit-identical.
 #include "../../../include/liteasr_io.h"
+#include "io_error.h"
 
 #include <fcntl.h>
 #include <unistd.h>
@@ -25,12 +26,8 @@
 
 namespace {
 
-thread_local std::string g_err;
-
-int fail(const std::string& msg) {
-  g_err = msg;
-  return -1;
-}
+using lasr_io::fail;
+using lasr_io::g_err;
 
 template <typename T>
 T bswap(T v) {

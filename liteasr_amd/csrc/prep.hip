@@ -12,6 +12,8 @@
 // argument (fixed), a device scalar (a captured graph replays whatever the host wrote there),
 // or drawn on the device per step from (seed, the step counter) -- the dynamic-chunk
 // training mode, replayable inside a graph.
+#include <algorithm>
+
 #include "common.h"
 
 LASR_DEV int64_t floordiv(int64_t a, int64_t b) {
@@ -145,4 +147,51 @@ extern "C" int lasr_u2_prep(const int64_t* xlens, const int64_t* ys, const int64
                             int32_t* pred_len, int32_t* ylen32, void* stream) {
   return lasr_u2_prep_ld(xlens, ys, ylens, B, Tx, L, Tsub, sos, eos, chunk, ys_in, tgt, tgt_ctc, dec_mask,
                          L + 1, enc_mask, Tsub, pred_len, ylen32, stream);
+}
+
+// ---- 16-bit PCM -> fp32 waveform (the pretraining batch, copied to HBM as int16) ----------
+// out[i] = pcm[i] * 2^-15, exact in fp32 (what soundfile.read returns for PCM_16, cast to
+// float).  A streaming pass: a lane loads 16 B (8 samples) and stores 2 x 16 B; the samples
+// before the first 16-byte boundary of pcm and the last n mod 8 go one per lane.  out is only
+// known to be 4-byte aligned at the first vector (it is offset by the same head as pcm), so its
+// vectors are typed with that alignment; the target stores them as dwordx4 all the same.
+typedef float pcm_f4 __attribute__((ext_vector_type(4), aligned(4)));
+
+__global__ void pcm_to_float_kernel(const int16_t* __restrict__ pcm, float* __restrict__ out, int head,
+                                    int64_t nvec, int tail) {
+  constexpr float S = 1.0f / 32768.0f;
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g < nvec) {
+    const int64_t i = head + 8 * g;
+    const uint4 u = *reinterpret_cast<const uint4*>(pcm + i);
+    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+    float v[8];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      v[2 * q] = (float)(int16_t)(w[q] & 0xFFFFu) * S;
+      v[2 * q + 1] = (float)((int32_t)w[q] >> 16) * S;
+    }
+    pcm_f4* o = reinterpret_cast<pcm_f4*>(out + i);
+    o[0] = (pcm_f4){v[0], v[1], v[2], v[3]};
+    o[1] = (pcm_f4){v[4], v[5], v[6], v[7]};
+  }
+  if (g < head) out[g] = (float)pcm[g] * S;
+  if (g < tail) {
+    const int64_t i = head + 8 * nvec + g;
+    out[i] = (float)pcm[i] * S;
+  }
+}
+
+extern "C" int lasr_pcm_to_float(const int16_t* pcm, int64_t n, float* out, void* stream) {
+  LASR_CHECK_ARG(n >= 0, "lasr_pcm_to_float: negative n");
+  if (n == 0) return LASR_OK;
+  LASR_CHECK_ARG(pcm && out, "lasr_pcm_to_float: null pointer");
+  LASR_CHECK_ARG(((uintptr_t)pcm & 1) == 0 && ((uintptr_t)out & 3) == 0, "lasr_pcm_to_float: misaligned pointer");
+  const int64_t head = std::min<int64_t>(n, (int64_t)((16 - ((uintptr_t)pcm & 15)) & 15) / 2);
+  const int64_t nvec = (n - head) / 8;
+  const int64_t tail = n - head - 8 * nvec;
+  const int64_t blocks = cdiv(std::max<int64_t>(nvec, 8), 256);  // head and tail (< 8 each) ride in block 0
+  LASR_CHECK_ARG(blocks <= 0x7FFFFFFF, "lasr_pcm_to_float: n too large for one launch");
+  pcm_to_float_kernel<<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(pcm, out, (int)head, nvec, (int)tail);
+  return lasr_check_launch("pcm_to_float");
 }

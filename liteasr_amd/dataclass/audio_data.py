@@ -1,16 +1,17 @@
 """Per-utterance record of a dataset (the Audio record of liteasr/dataclass/audio_data.py).
 
-Holds where the utterance's feature matrix lives (``fd``: a Kaldi "ark:offset" path,
-decoded lazily by the native reader), its frame count and its token ids.  Positional
-construction order (fd, start, shape, tokenids, text) is the reference's.  Raw-waveform
-entries (``start`` not None, from wav.scp/segments) are outside the feature training path
-and raise.
+Holds where the utterance's input lives, its length and its token ids.  A feature entry
+(``start`` None) has ``fd`` a Kaldi "ark:offset" path and ``shape`` frames; a raw-waveform
+entry (from wav.scp / segments, the pretraining path) has ``fd`` a WAV file, ``start`` its
+first sample and ``shape`` samples.  Both are decoded lazily by the native readers.
+Positional construction order (fd, start, shape, tokenids, text) is the reference's.
 """
 
 from typing import Optional, Tuple
 
 import torch
 
+from ..utils import wavio
 from ..utils.kaldiio import load_mat
 
 
@@ -30,7 +31,10 @@ class Audio(object):
     @property
     def x(self) -> torch.Tensor:
         if self.start is not None:
-            raise NotImplementedError("raw-waveform input (wav.scp) is outside the feature training path")
+            # samples[start : start + xlen] of soundfile's PCM_16 decode (int16 / 32768, exact in
+            # float32), audio_data.py:30-33; a window past the end of the file comes back shorter
+            pcm, got = wavio.read(self.fd, self.start, max(self.xlen, 0))
+            return torch.from_numpy(pcm[:got].astype("float32") / 32768.0)
         return torch.from_numpy(load_mat(self.fd))
 
     @property

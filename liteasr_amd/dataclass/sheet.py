@@ -1,9 +1,16 @@
-"""Kaldi data-directory sheets (liteasr/dataclass/sheet.py:19-123): feats.scp +
-utt2num_frames (AudioSheet) and text (TextSheet), iterated line by line in step."""
+"""Kaldi data-directory sheets (liteasr/dataclass/sheet.py:19-123): AudioSheet over feats.scp +
+utt2num_frames (features, taken first when present) or wav.scp with or without segments (raw
+waveforms, the pretraining path), and TextSheet over text; iterated line by line.
+
+AudioSheet yields (uttid, where, start, length): a feature entry has start None and its frame
+count; a segment has its first sample round(start * 16000) and the reference's length
+end - start - 1 (sheet.py:75-77); a whole recording has start 0 and its sample count, which
+comes from the WAV header (lasr_wav_probe) where the reference decodes the file to count."""
 
 import os
 from typing import Optional
 
+from ..utils import wavio
 from .vocab import Vocab
 
 
@@ -27,11 +34,45 @@ class AudioSheet(object):
             self.segments = None
             self.lines = _lines(self.scp)
         elif "wav.scp" in files:
-            raise NotImplementedError("wav.scp input is outside the feature training path (feats.scp only)")
+            self.scp = f"{data_dir}/wav.scp"
+            self.segments = f"{data_dir}/segments" if "segments" in files else None
+            self.lines = max(_lines(self.scp), _lines(self.segments))
         else:
             raise FileNotFoundError(f"wav.scp not found in {data_dir}")
 
     def __iter__(self):
+        if self.scp.endswith("feats.scp"):
+            return self._features()
+        return self._segments() if self.segments is not None else self._recordings()
+
+    @staticmethod
+    def _wav_entries(fscp):
+        for line in fscp:
+            entry = line.strip().split(None, 1)
+            if len(entry) != 2:
+                raise ValueError(f"Invalid line is found:\n>   {line}")
+            if entry[1].rstrip().endswith("|"):
+                raise NotImplementedError(f"wav.scp pipe input is not supported: {entry[1]}")
+            yield entry
+
+    def _segments(self):
+        with open(self.segments, "r") as fseg, open(self.scp, "r") as fscp:
+            fds = dict(self._wav_entries(fscp))
+            for line in fseg:
+                entry = line.strip().split()
+                if len(entry) != 4:
+                    raise ValueError(f"Invalid line is found:\n>   {line}")
+                uttid, wavid, start, end = entry
+                start = round(float(start) * 16000)
+                end = round(float(end) * 16000)
+                yield uttid, fds[wavid], start, end - start - 1
+
+    def _recordings(self):
+        with open(self.scp, "r") as fscp:
+            for wavid, wavfd in self._wav_entries(fscp):
+                yield wavid, wavfd, 0, wavio.probe(wavfd).frames
+
+    def _features(self):
         with open(self.scp, "r") as fscp, open(self.shape, "r") as fshp:
             while True:
                 a, b = fscp.readline(), fshp.readline()

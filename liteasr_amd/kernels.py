@@ -1034,6 +1034,19 @@ def cast(src, dst):
     N.call("lasr_cast", ptr(src), dt(src), ptr(dst), dt(dst), src.numel(), stream())
 
 
+def pcm_to_float(pcm, out=None):
+    """16-bit PCM -> fp32 waveform, pcm * 2^-15 (lasr_pcm_to_float).  ``pcm``: a contiguous int16
+    device tensor (any 2-byte-aligned view); returns ``out`` (fp32, the same shape)."""
+    if pcm.dtype != torch.int16 or not pcm.is_contiguous() or pcm.device.type != "cuda":
+        raise TypeError("pcm_to_float: a contiguous int16 device tensor is needed")
+    if out is None:
+        out = torch.empty(pcm.shape, dtype=torch.float32, device=pcm.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != pcm.numel():
+        raise TypeError("pcm_to_float: out must be a contiguous fp32 tensor of the same size")
+    N.call("lasr_pcm_to_float", ptr(pcm), pcm.numel(), ptr(out), stream())
+    return out
+
+
 def scale_add(a, b, sa, sb, out):
     N.call("lasr_scale_add", ptr(a), dt(a), ptr(b), dt(b) if b is not None else 0, sa, sb,
            ptr(out), dt(out), out.numel(), stream())

@@ -2,7 +2,9 @@
 
 Same config schema, registry name ("wav2vec2"), ``state_dict()`` keys / shapes, construction
 order and initialisation as the reference: ``model(source (B, S)) -> logits (M B, N + 1)``,
-with the ``wav2vec`` criterion (criterions/wav2vec_loss.py) on top.  The path: feature
+with the ``wav2vec`` criterion (criterions/wav2vec_loss.py) on top.  ``source`` is the fp32
+waveform, or the 16-bit PCM batch of the pretraining collator (int16: converted on the device by
+``lasr_pcm_to_float``, sample / 32768, before anything else).  The path: feature
 extractor (layer 0 a direct kernel, the others GEMMs over a strided view), layer_norm,
 linear_input, mask embedding, grouped positional convolution, embed_norm, the pre-norm
 Transformer layers of nets/functional.py driven with batch = T' and time = B (the reference
@@ -248,6 +250,8 @@ class Wav2Vec2(LiteasrModel):
         if not float(c.mask_prob) > 0:
             raise NotImplementedError("wav2vec2: mask_prob must be > 0 (the reference's forward needs the mask)")
         _require_hip(self, source)
+        if source.dtype == torch.int16:  # 16-bit PCM as the pretraining collator delivers it
+            source = K.pcm_to_float(source.contiguous())
         dev = source.device
         B = source.shape[0]
         T = self.feature_extractor.out_frames(source.shape[1])

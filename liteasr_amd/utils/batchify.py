@@ -8,8 +8,10 @@ each one, whether the open minibatch is closed first:
   int(batch_size / (1 + max(int(xlen / max_len_in), int(ylen / max_len_out))))).
 * ``FrameBatch`` -- it closes when (size + 1) x max length would exceed any of the
   enabled frame budgets max_frame_in / max_frame_out / max_frame_inout.
+* ``Wav2VecBatch`` -- raw waveforms: it closes when (size + 1) x min(250000, shortest
+  utterance) would exceed max_batch_frame samples (the collator crops to that length).
 
-Both keep the reference's edge behaviour: the "closes first?" test also runs on an empty
+All keep the reference's edge behaviour: the "closes first?" test also runs on an empty
 minibatch, so an utterance that alone exceeds a frame budget emits an empty minibatch
 before it (it still gets a minibatch of its own).  ``policy.data[i]`` / ``policy[i]`` is
 the i-th minibatch as a list of utterance indices.
@@ -67,3 +69,23 @@ class FrameBatch(BatchifyPolicy):
         ymax = max([s.ylen for s in open_samples] + [nxt.ylen])
         budgets = ((c.max_frame_in, xmax), (c.max_frame_out, ymax), (c.max_frame_inout, xmax + ymax))
         return any(limit and length * n > limit for limit, length in budgets)
+
+
+class Wav2VecBatch(BatchifyPolicy):
+    """Raw-waveform minibatches (batchify.py:162-182).  The collator crops a minibatch to its
+    shortest utterance, capped at ``min_frame`` samples, so it closes when (size + 1) x that
+    crop would exceed ``max_batch_frame``.  The reference fixes max_batch_frame at 1400000
+    ("should be configurable"); here ``dataset.max_batch_frame`` overrides it when set."""
+
+    min_frame: int = 250000
+    max_batch_frame: int = 1400000
+
+    def __init__(self, dataset_cfg):
+        super().__init__(dataset_cfg)
+        get = dataset_cfg.get if isinstance(dataset_cfg, dict) else lambda k, d=None: getattr(dataset_cfg, k, d)
+        if get("max_batch_frame", None):
+            self.max_batch_frame = int(get("max_batch_frame"))
+
+    def _closes_before(self, open_samples, nxt) -> bool:
+        crop = min([self.min_frame] + [s.xlen for s in open_samples] + [nxt.xlen])
+        return (len(open_samples) + 1) * crop > self.max_batch_frame
