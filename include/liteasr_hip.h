@@ -646,6 +646,25 @@ int lasr_u2_prep_chunk(const int64_t* xlens, const int64_t* ys, const int64_t* y
  * out 4-byte alignment only; n elements, one launch. */
 int lasr_pcm_to_float(const int16_t* pcm, int64_t n, float* out, void* stream);
 
+/* Kaldi fbank front end of task=asr on raw audio (csrc/fbank.hip; the reference has none: its
+ * Audio.x hands bare samples to feature models).  compute-fbank-feats with --snip-edges=true
+ * --dither=0 --remove-dc-offset=true --preemphasis-coefficient=0.97 --window-type=povey
+ * --use-power=true --use-energy=false --low-freq=20 --high-freq=0 --num-mel-bins=F, 25 ms / 10 ms
+ * frames at 16 kHz (400 / 160 samples, 512-point FFT), samples at int16 scale.
+ *   pcm [B] rows of S int16 samples, row_stride elements apart (2-byte alignment is enough);
+ *   nframes [B] int32 (device): frames of each row, clamped to [0, max_frames] by the kernel;
+ *   max_frames: the host's bound on them; S >= 160 (max_frames - 1) + 400 is checked here, so
+ *     no sample past a row's S is read whatever nframes holds;
+ *   tab fp32 [2048] (8-byte aligned), seg int32 [F + 2]: the window, twiddle and mel tables as
+ *     liteasr_amd.kernels.fbank_tables lays them out (computed in float64 on the host);
+ *   mean, istd fp32 [F] or both NULL: out = (log mel - mean) istd;
+ *   out fp32 [B][Tmax][F], every element written: rows t >= nframes[b] are 0, with CMVN too.
+ * Frame t of row b reads samples 160 t .. 160 t + 399 only.  1 <= F <= 128.  fp32 arithmetic;
+ * a frame's bits do not depend on b, t, Tmax, row_stride or the alignment of pcm. */
+int lasr_fbank(const int16_t* pcm, int64_t row_stride, int B, int64_t S, const int32_t* nframes,
+               int max_frames, const float* tab, const int32_t* seg, int F, const float* mean,
+               const float* istd, float* out, int Tmax, void* stream);
+
 /* ------------------------------------------------------------------------
  * SpecAugment (liteasr/utils/transform/spec_augment.py:14-125; applied per utterance in
  * the reference's DataLoader workers, liteasr/dataset/asr_dataset.py:118).  Replaces the

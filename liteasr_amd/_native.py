@@ -214,6 +214,7 @@ SIGNATURES = {
     "lasr_u2_prep_chunk": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _u, _i,
                            _p, _p, _p, _p, _i, _p, _p, _i, _p, _p, _p],
     "lasr_pcm_to_float": [_p, _l, _p, _p],
+    "lasr_fbank": [_p, _l, _i, _l, _p, _i, _p, _p, _i, _p, _p, _p, _i, _p],
     "lasr_sumsq_nparts": [_l],
     "lasr_sumsq_partial": [_p, _l, _p, _l, _p],
     "lasr_adam_step": [_p, _p, _i, _p, _p, _p, _l, _p, _i, _p, _f, _i, _f, _f, _f, _f, _f, _f,

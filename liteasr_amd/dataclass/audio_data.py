@@ -48,3 +48,35 @@ class Audio(object):
     @property
     def ylen(self) -> int:
         return 0 if self.tokenids is None else len(self.tokenids)
+
+
+class WavAudio(Audio):
+    """An utterance of task=asr read from wav.scp: the record keeps its sample window (``start``,
+    ``shape`` samples) and its length for batching, ``xlen``, is the frame count of the fbank
+    front end.  ``x`` is the window as stored, 16-bit PCM: the features are computed on the
+    device (liteasr_amd/utils/frontend.py)."""
+
+    __slots__ = ("frames",)
+
+    def __init__(self, fd, start, shape, tokenids, text, frames: int):
+        super().__init__(fd, start, shape, tokenids, text)
+        self.frames = frames
+
+    def __repr__(self):
+        return (f"WavAudio(fd={self.fd!r}, start={self.start}, shape={self.shape}, frames={self.frames}, "
+                f"ylen={self.ylen})")
+
+    def __eq__(self, other):
+        return isinstance(other, WavAudio) and all(getattr(self, k) == getattr(other, k)
+                                                   for k in Audio.__slots__ + WavAudio.__slots__)
+
+    @property
+    def x(self) -> torch.Tensor:
+        pcm, got = wavio.read(self.fd, self.start, self.shape)
+        if got < self.shape:
+            raise ValueError(f"{self.fd}: {got} of the utterance's {self.shape} samples are on disk")
+        return torch.from_numpy(pcm)
+
+    @property
+    def xlen(self) -> int:
+        return self.frames

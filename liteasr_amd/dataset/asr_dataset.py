@@ -12,6 +12,15 @@ collator only draws the augmentation plan and returns it as a fifth element; the
 applies it to the batch on the GPU.  (The reference's ``memory_save`` pickle dump of
 batches is not carried over: it serialises Python objects to disk and is not on the step
 path.)
+
+Raw audio (a directory with wav.scp and no feats.scp; the reference has no such path for
+task=asr): every record keeps its sample window and is batched by its fbank frame count
+``1 + (n - 400) // 160``, so the SeqBatch / FrameBatch budgets mean frames as they do for
+feats.scp; utterances below 400 samples (no frame) are dropped with one logged count;
+``feat_dim`` is the front end's ``num_mel_bins``.  The collator reads the minibatch with one
+native call (lasr_wav_read_batch) into a zero-padded int16 (B, Smax) tensor and returns it with
+the frame counts; the trainer turns it into features on the GPU (liteasr_amd/utils/frontend.py)
+before the SpecAugment plan, drawn here from the frame counts as for features, is applied.
 """
 
 import logging
@@ -20,9 +29,11 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from ..dataclass.audio_data import Audio
+from ..dataclass.audio_data import Audio, WavAudio
 from ..dataclass.sheet import AudioSheet, TextSheet
+from ..utils import wavio
 from ..utils.batchify import FrameBatch, SeqBatch
+from ..utils.frontend import num_frames, used_samples
 from ..utils.kaldiio import read_padded
 from ..utils.transform import PostProcess
 from .liteasr_dataset import LiteasrDataset
@@ -32,7 +43,7 @@ logger = logging.getLogger(__name__)
 
 class AudioFileDataset(LiteasrDataset):
     def __init__(self, split: str, data_dir: str, delimiter: Optional[str], dataset_cfg, postprocess_cfg, vocab,
-                 keep_raw=False, memory_save=False):
+                 keep_raw=False, memory_save=False, num_mel_bins: int = 80):
         super().__init__()
         if memory_save:
             raise NotImplementedError("memory_save (pickled batch dumps) is not supported")
@@ -45,10 +56,19 @@ class AudioFileDataset(LiteasrDataset):
         audios = AudioSheet(data_dir)
         texts = TextSheet(data_dir, vocab=vocab, delimiter=delimiter)
         assert len(audios) == len(texts)
+        self.wav = audios.scp.endswith("wav.scp")  # raw audio: features come from the device front end
+        short = 0
         for (uttid, fd, start, shape), (uttid_t, ids, text) in zip(audios, texts):
             assert uttid_t == uttid
-            self.data.append(Audio(fd, start, shape, ids, text if keep_raw else None))
-        self.feat_dim = self.data[0].x.shape[-1]
+            if not self.wav:
+                self.data.append(Audio(fd, start, shape, ids, text if keep_raw else None))
+            elif num_frames(shape) == 0:
+                short += 1
+            else:
+                self.data.append(WavAudio(fd, start, shape, ids, text if keep_raw else None, num_frames(shape)))
+        if short:
+            logger.warning("{}: dropped {} utterance(s) shorter than one 25 ms frame".format(data_dir, short))
+        self.feat_dim = int(num_mel_bins) if self.wav else self.data[0].x.shape[-1]
         if dataset_cfg is not None:
             self.batchify(dataset_cfg)
 
@@ -83,7 +103,11 @@ class AudioFileDataset(LiteasrDataset):
             # calls); the pixels are produced on the GPU by the trainer (apply_batch)
             plan = post.plan_batch(xlens.tolist(), self.feat_dim)
             post = None
-        if post is None and all(s.start is None for s in batch):
+        if self.wav:
+            if post is not None:
+                raise NotImplementedError("raw-audio batches take device-side postprocessing only (spec_aug)")
+            xs = self._collate_pcm(batch)
+        elif post is None and all(s.start is None for s in batch):
             tmax = int(xlens.max()) if B else 0
             xs = torch.empty(B, tmax, self.feat_dim, dtype=torch.float32)
             _, lens = read_padded([s.fd for s in batch], tmax, self.feat_dim, out=xs.numpy())
@@ -100,6 +124,21 @@ class AudioFileDataset(LiteasrDataset):
         if plan is not None:
             return xs, xlens, ys, ylens, plan
         return xs, xlens, ys, ylens
+
+    @staticmethod
+    def _collate_pcm(batch: List[WavAudio]):
+        """int16 (B, Smax), Smax the longest sample count; zero past every utterance's own samples."""
+        B = len(batch)
+        smax = max((s.shape for s in batch), default=0)
+        xs = torch.empty(B, smax, dtype=torch.int16)
+        arr = xs.numpy()
+        _, got = wavio.read_batch([s.fd for s in batch], [s.start for s in batch], smax, out=arr)
+        for i, s in enumerate(batch):
+            if got[i] < used_samples(s.frames):
+                raise ValueError("{}: {} samples from {} on disk, {} frames need {}".format(
+                    s.fd, int(got[i]), s.start, s.frames, used_samples(s.frames)))
+            arr[i, s.shape:] = 0  # a segment's window may run on into the recording
+        return xs
 
     def __getitem__(self, index):
         if self.batchify_policy is not None:

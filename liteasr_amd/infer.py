@@ -10,6 +10,10 @@ or an average), and per test set one block per utterance
 
 followed by ``Error rate: <errors> / <reference length> = <percent>``.
 
+A test set may be a raw-audio directory (wav.scp, no feats.scp): its utterances reach
+``task.inference`` as int16 PCM and go through the task's device front end (``task.frontend``:
+Kaldi fbank and optional CMVN) there; they are ordered and graph-planned by their frame counts.
+
 Differences from the reference, on purpose:
 
 * it decodes utterance by utterance (``load_dataset("test", ..., None, ...)``).  The reference

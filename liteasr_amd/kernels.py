@@ -1047,6 +1047,104 @@ def pcm_to_float(pcm, out=None):
     return out
 
 
+# Kaldi fbank front end (csrc/fbank.hip).  The Kaldi options are fixed: 16 kHz, 25 ms / 10 ms
+# frames, snip-edges, no dither, DC removal, pre-emphasis 0.97, povey window, 512-point FFT,
+# power spectrum, mel filters from 20 Hz to the Nyquist frequency, no energy, no VTLN.
+FBANK_FRAME_LEN, FBANK_FRAME_SHIFT, FBANK_NFFT, FBANK_FS = 400, 160, 512, 16000
+FBANK_LOW_FREQ, FBANK_MAX_BINS = 20.0, 128
+_FBANK_TABLES = {}
+
+
+def fbank_num_frames(nsamples: int) -> int:
+    """snip-edges frame count of an utterance of ``nsamples`` samples."""
+    return 0 if nsamples < FBANK_FRAME_LEN else 1 + (nsamples - FBANK_FRAME_LEN) // FBANK_FRAME_SHIFT
+
+
+def fbank_tables(num_mel_bins: int):
+    """The kernel's tables, computed in float64 on the host: (tab float32 [2048], seg int32 [F + 2]).
+    tab: the povey window padded to 512; exp(-2 pi i m / 256) and exp(-2 pi i k / 512) for m, k <
+    256, interleaved (re, im); then per FFT bin k < 256 its rising and its falling mel weight.
+    The F + 2 mel edges cut the bins into F + 1 runs, run j = the bins with edge[j] < mel(bin) <=
+    edge[j + 1] (the last run stops below the last edge) starting at seg[j], seg[F + 1] its end;
+    filter f sums its rising weights over run f and its falling weights over run f + 1, so a
+    bin lies in at most two triangles and carries one weight for each."""
+    import numpy as np
+
+    F = int(num_mel_bins)
+    if not 1 <= F <= FBANK_MAX_BINS:
+        raise ValueError(f"fbank: num_mel_bins must be in 1..{FBANK_MAX_BINS}, got {F}")
+    half = FBANK_NFFT // 2
+    tab = np.zeros(2048, dtype=np.float64)
+    i = np.arange(FBANK_FRAME_LEN, dtype=np.float64)
+    tab[:FBANK_FRAME_LEN] = (0.5 - 0.5 * np.cos(2.0 * np.pi * i / (FBANK_FRAME_LEN - 1))) ** 0.85
+    k = np.arange(half, dtype=np.float64)
+    for base, n in ((512, half), (1024, FBANK_NFFT)):
+        tab[base:base + 512:2] = np.cos(2.0 * np.pi * k / n)
+        tab[base + 1:base + 512:2] = -np.sin(2.0 * np.pi * k / n)
+
+    def mel(f):
+        return 1127.0 * np.log(1.0 + f / 700.0)
+
+    edges = np.linspace(mel(FBANK_LOW_FREQ), mel(FBANK_FS / 2.0), F + 2)
+    m = mel(k * (FBANK_FS / FBANK_NFFT))
+    seg = np.searchsorted(m, edges, side="right").astype(np.int32)  # first bin with mel > edge
+    seg[F + 1] = np.searchsorted(m, edges[F + 1], side="left")  # the last edge itself is outside
+    for j in range(F + 1):
+        lo, hi = int(seg[j]), int(seg[j + 1])
+        width = edges[j + 1] - edges[j]
+        tab[1536 + lo:1536 + hi] = (m[lo:hi] - edges[j]) / width
+        tab[1792 + lo:1792 + hi] = (edges[j + 1] - m[lo:hi]) / width
+    return tab.astype(np.float32), seg
+
+
+def _fbank_device_tables(F: int, device):
+    key = (int(F), torch.device(device).index)
+    t = _FBANK_TABLES.get(key)
+    if t is None:
+        tab, seg = fbank_tables(F)
+        t = (torch.from_numpy(tab).to(device), torch.from_numpy(seg).to(device))
+        _FBANK_TABLES[key] = t
+    return t
+
+
+def fbank(pcm, nframes, num_mel_bins=80, cmvn=None, out=None, max_frames=None):
+    """Kaldi log-mel filterbank features of a batch of 16-bit PCM (lasr_fbank): ``pcm`` an int16
+    device tensor (B, S) with contiguous rows (any row stride), ``nframes`` int32 [B] on the
+    device, ``cmvn`` None or (mean, istd) fp32 [F] device tensors.  Returns ``out``, fp32
+    (B, Tmax, F) contiguous, every element written: rows t >= nframes[b] are zero.  Tmax is
+    out.shape[1], or the largest frame count.  ``max_frames``: the caller's host-side bound on
+    nframes (frame counts above it are clamped by the kernel); None reads it back from the
+    device, one synchronisation.  S must hold the samples of max_frames frames."""
+    if (pcm.dtype != torch.int16 or pcm.dim() != 2 or pcm.device.type != "cuda"
+            or (pcm.shape[1] > 1 and pcm.stride(1) != 1)):
+        raise TypeError("fbank: an int16 (B, S) device tensor with contiguous rows is needed")
+    B, S = pcm.shape
+    if (nframes.dtype != torch.int32 or nframes.device != pcm.device or nframes.shape != (B,)
+            or not nframes.is_contiguous()):
+        raise TypeError("fbank: nframes must be an int32 [B] tensor on the device of pcm")
+    F = int(num_mel_bins)
+    tab, seg = _fbank_device_tables(F, pcm.device)
+    if max_frames is None:
+        max_frames = int(nframes.max()) if B else 0
+    max_frames = max(int(max_frames), 0)
+    if max_frames and S < FBANK_FRAME_SHIFT * (max_frames - 1) + FBANK_FRAME_LEN:
+        raise ValueError(f"fbank: {S} samples per row cannot hold {max_frames} frames")
+    mean = istd = None
+    if cmvn is not None:
+        mean, istd = cmvn
+        for v in (mean, istd):
+            if v.dtype != torch.float32 or v.device != pcm.device or v.shape != (F,) or not v.is_contiguous():
+                raise TypeError("fbank: cmvn must be two fp32 [F] tensors on the device of pcm")
+    if out is None:
+        out = torch.empty(B, max_frames, F, dtype=torch.float32, device=pcm.device)
+    elif (out.dtype != torch.float32 or out.device != pcm.device or out.dim() != 3 or out.shape[0] != B
+          or out.shape[2] != F or not out.is_contiguous()):
+        raise TypeError("fbank: out must be a contiguous fp32 (B, Tmax, F) tensor on the device of pcm")
+    N.call("lasr_fbank", ptr(pcm), pcm.stride(0) if B > 1 else S, B, S, ptr(nframes), max_frames, ptr(tab),
+           ptr(seg), F, ptr(mean), ptr(istd), ptr(out), out.shape[1], stream())
+    return out
+
+
 def scale_add(a, b, sa, sb, out):
     N.call("lasr_scale_add", ptr(a), dt(a), ptr(b), dt(b) if b is not None else 0, sa, sb,
            ptr(out), dt(out), out.numel(), stream())

@@ -1,4 +1,10 @@
-"""ASR task (liteasr/tasks/asr.py:23-98): vocabulary, feature datasets, model saving."""
+"""ASR task (liteasr/tasks/asr.py:23-98): vocabulary, feature datasets, model saving.
+
+Data directories with feats.scp are read as the reference reads them.  A directory with wav.scp
+and no feats.scp is raw audio: the task's front end (``task.frontend``: Kaldi fbank with
+``num_mel_bins`` filters and optional global CMVN statistics, liteasr_amd/utils/frontend.py)
+computes the features on the device, in the trainer and in ``inference``.  Every other Kaldi
+fbank option is fixed at the value documented there; ``dither`` other than 0 is refused."""
 
 import inspect
 import logging
@@ -7,12 +13,24 @@ from dataclasses import dataclass, field
 from pathlib import Path
 from typing import List, Optional, Union
 
+import torch
+
 from ..config import MISSING, LiteasrDataclass
 from ..dataclass.vocab import Vocab
 from ..dataset import AudioFileDataset
+from ..utils.frontend import Fbank, num_frames
 from . import LiteasrTask, register_task
 
 logger = logging.getLogger(__name__)
+
+
+@dataclass
+class FrontendConfig(LiteasrDataclass):
+    """liteasr_amd extension: the device front end of raw-audio (wav.scp) data directories."""
+
+    num_mel_bins: int = field(default=80)
+    cmvn: Optional[str] = field(default=None)  # Kaldi global CMVN statistics, 2 x (num_mel_bins + 1)
+    dither: float = field(default=0.0)  # only 0 is supported
 
 
 @dataclass
@@ -23,6 +41,15 @@ class ASRConfig(LiteasrDataclass):
     test: List[str] = field(default_factory=list)
     delimiter: Optional[str] = field(default=None)
     save_dir: str = field(default="ckpts")
+    frontend: FrontendConfig = field(default_factory=FrontendConfig)
+
+
+def _frontend_of(cfg) -> Fbank:
+    fe = cfg.get("frontend") if isinstance(cfg, dict) else getattr(cfg, "frontend", None)
+    if fe is None:
+        return Fbank()
+    get = fe.get if isinstance(fe, dict) else lambda k, d=None: getattr(fe, k, d)
+    return Fbank(num_mel_bins=get("num_mel_bins", 80), cmvn=get("cmvn", None), dither=float(get("dither", 0.0) or 0.0))
 
 
 @register_task("asr", dataclass=ASRConfig)
@@ -34,6 +61,7 @@ class ASRTask(LiteasrTask):
         Path(self.save_dir).mkdir(parents=True, exist_ok=True)
         self.vocab_size = len(self.vocab)
         self.feat_dim = 0
+        self.frontend = _frontend_of(cfg)
 
     def load_dataset(self, split: str, data_dir: Union[str, list], dataset_cfg=None, postprocess_cfg=None,
                      memory_save: bool = False):
@@ -43,7 +71,7 @@ class ASRTask(LiteasrTask):
             logger.info("loading {} data from {}".format(split, d))
             return AudioFileDataset(split=split, data_dir=d, delimiter=self.cfg.delimiter, dataset_cfg=dataset_cfg,
                                     postprocess_cfg=postprocess_cfg, vocab=self.vocab, keep_raw=split == "test",
-                                    memory_save=memory_save)
+                                    memory_save=memory_save, num_mel_bins=self.frontend.num_mel_bins)
 
         if isinstance(data_dir, str):
             self.datasets[split] = one(data_dir)
@@ -56,7 +84,13 @@ class ASRTask(LiteasrTask):
 
     def inference(self, x, model, encoder_graph=None):
         """encoder_graph (None: the model's default) is handed to models whose ``inference``
-        takes it: whether this utterance's frame count is worth an encoder graph capture."""
+        takes it: whether this utterance's frame count is worth an encoder graph capture.
+        ``x``: (1, T, F) features, or (1, n) int16 PCM of a raw-audio utterance on the device, which
+        goes through the task's front end first (every sample of it is used)."""
+        if x.dtype == torch.int16:
+            frames = num_frames(x.shape[-1])
+            x = self.frontend(x, torch.full((x.shape[0],), frames, dtype=torch.int32, device=x.device),
+                              max_frames=frames)
         if encoder_graph is None or "encoder_graph" not in inspect.signature(model.inference).parameters:
             ids = model.inference(x)
         else:

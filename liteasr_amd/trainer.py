@@ -110,13 +110,26 @@ class Trainer(object):
         opt.step()
         return True
 
+    def _features(self, batch):
+        """The batch on the device.  A raw-audio batch of the ASR task (int16 PCM with frame counts,
+        AudioFileDataset over wav.scp) becomes the fp32 (B, T, F) feature batch of the task's front
+        end there; every other batch (features, or the pretraining task's waveforms, which carry
+        no lengths) is only copied."""
+        raw = (isinstance(batch, (tuple, list)) and len(batch) >= 2 and torch.is_tensor(batch[0])
+               and batch[0].dtype == torch.int16 and torch.is_tensor(batch[1]))
+        tmax = int(batch[1].max()) if raw and batch[1].numel() else 0  # on the host: no read-back later
+        batch = to_device(batch, self.device)
+        if raw:
+            batch = (self.task.frontend(batch[0], batch[1], max_frames=tmax),) + tuple(batch[1:])
+        return batch
+
     def run(self):
         accum = self.cfg.optimization.accum_grad
         for i, batch in enumerate(self.train_iter, start=1):
             self.event_manager.trigger_epoch_events(self)
             if self.stop():
                 break
-            batch = to_device(batch, self.device)
+            batch = self._features(batch)
             if len(batch) == 5:  # device-side postprocess (SpecAugment plan from the collator)
                 xs, xlens, ys, ylens, plan = batch
                 xs = self._train_post.apply_batch(xs, xlens, plan)
@@ -153,7 +166,7 @@ class Trainer(object):
         with torch.no_grad():
             losses = []
             for bat in self.valid_iter:
-                bat = to_device(bat, self.device)
+                bat = self._features(bat)
                 loss = self.criterion(self.model, *bat)
                 if dist.is_initialized():
                     dist.reduce(loss, dst=0)
