@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import kernels as K
+from .graph_step import collect_before_capture
 from .nets import functional as FN
 
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libliteasr_decode.so")
@@ -98,6 +99,7 @@ def encode(model, x, graph=True, fp32=False):
             _encode_eager(model, static, fp32)
         cur.wait_stream(side)
         torch.cuda.synchronize()
+        collect_before_capture()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             h, T = _encode_eager(model, static, fp32)
@@ -285,6 +287,7 @@ class _Rescore:
             self.launches(model)
         cur.wait_stream(side)
         torch.cuda.synchronize()
+        collect_before_capture()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             self.keep = self.launches(model)
@@ -456,6 +459,7 @@ class _RnntSearch:
                     K.rnnt_search_expand(self.args, 0)
             cur.wait_stream(side)
             torch.cuda.synchronize()
+            collect_before_capture()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 for _ in range(_BEAM):

@@ -32,6 +32,8 @@ advance training.
 
 from __future__ import annotations
 
+import gc
+
 import torch
 
 from . import kernels as K
@@ -40,6 +42,16 @@ from . import kernels as K
 # process group's watchdog thread polls the events of earlier (finished) collectives
 # with hipEventQuery, which the default "global" mode turns into a capture error.
 _MODE = "thread_local"
+
+
+def collect_before_capture():
+    """Run the cyclic garbage collector; call it right before a stream capture begins.  A
+    dropped model is a reference cycle, so the hipGraphs cached on it (GraphStep,
+    decoding.encode) die only when the collector runs, and torch.cuda.CUDAGraph's destructor
+    synchronises the device: inside another graph's capture that is a capture error thrown
+    from a destructor, which aborts the process.  Young garbage made during the capture holds
+    no graph.  (torch.cuda.graph collects here itself only with force_cudagraph_gc.)"""
+    gc.collect()
 
 
 def _new_graph():
@@ -193,6 +205,7 @@ class GraphedTrainStep:
                     self._eager_once()
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
+            collect_before_capture()
             if self.ddp is None:
                 self.g1 = _new_graph()
                 with torch.cuda.graph(self.g1, capture_error_mode=_MODE):

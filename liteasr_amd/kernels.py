@@ -4,6 +4,11 @@ Every function here launches kernels from libliteasr_hip.so on the current HIP s
 (``torch.cuda.current_stream()``) and never synchronises, so a training step built
 from them can be captured into a hipGraph.  Tensors must live on the GPU; there is
 no CPU path (the CPU restatement lives in ``oracle/`` and is test-only).
+
+The one part that is not thin is the queue of a backward node's deferred work (``_Deferred``,
+``deferred_reductions``): it orders every weight-gradient launch and parameter-gradient reduction
+of a training step.  ``gemm`` hands it the dW GEMMs (``_queue_dw``); the backward wrappers hand it
+their partial sums (``_partials``, ``_defer`` / ``_reduce_or_defer``).
 """
 
 from __future__ import annotations
@@ -13,7 +18,7 @@ import os
 import ctypes as C
 import math
 from types import SimpleNamespace
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -63,21 +68,259 @@ WS = _Workspace()
 
 
 # --------------------------------------------------------- deferred reductions ---
+# The queue's policy switches are read from the module at call time (tests and tools set them).
+# Grouped weight gradients: dW GEMMs marked group=True inside a deferred_reductions block are
+# queued and launched at its end, one lasr_gemm_dw_group launch per planned tile (<= 32
+# problems each), before the reductions (tests set DW_GROUP = False to compare with lone launches).
+DW_GROUP = True
+# plan tile -> group (lasr_gemm_dw_group runs the 64 x 128 / 128 x 64 plans, the FFN-sized
+# weights, on 128 x 128 tiles)
+_GROUP_TILES = {(64, 64): (64, 64), (64, 128): (128, 128), (128, 64): (128, 128)}
+_GROUP_MAX = 32  # problems per lasr_gemm_dw_group launch (LASR_DW_GROUP_MAX)
+# grouped problems fill the chip together: each takes 1/div of the K slices the planner gives
+# a lone launch (fewer fp32 partial slabs to write and reduce); 128 x 128 groups keep half
+# (the other divisors measured slower)
+DW_GROUP_SPLIT_DIV = {(64, 64): 4, (128, 128): 2}
+# Direct grouped weight gradients: FFN-sized problems with >= this many full-K 128 x 128 tiles
+# (the d 512 FFN weights: 64 each, a group of four = 256 tiles) skip the K split and write the
+# gradient itself (beta = 1), no fp32 partial slab to write and reduce.  Measured at config 4
+# (VERDICT r05 item 3): 20.13 -> 20.74 ms per step, the full-K 128 x 128 tiles are L2-feed bound
+# where the 256 x 128 split-2 tiles are not (profiles/r06/step_ab_dw_direct_large_rejected.jsonl,
+# DESIGN §4); 0 = off.  tests/test_kernels_gpu.py::test_gemm_dw_group_direct pins the path.
+DW_DIRECT_MIN_TILES = 0
+# grouped dW blocks laid out longest K slice first (lasr_gemm_dw_group_order; same bits)
+DW_GROUP_LPT = True
+# Held weight-gradient GEMMs: inside a hold block the grouped dW GEMMs are queued without a
+# slab and launched where the held reductions are (tests set False to compare).
+DW_HOLD_GEMMS = True
+# A held family (one group tile) whose tiles at the flush fill the chip (>= the CU count) runs
+# serial-slice: one block per tile runs the planned K slices in order and writes the gradient
+# itself, the bits of slabs + lasr_reduce_multi.  Smaller families get their slabs
+# at the flush and take the slab path.  Counts only: the same on every step and rank.
+DW_SERIAL_MIN_TILES = 256
+# the waiting GEMMs are launched after this many hold blocks even inside a segment; 0 = at the
+# segment's end only.  4 layers of the small model are one full round of FFN tiles (256) and
+# measured best of 4 / 6 / whole segment on small, large and long (DESIGN §4,
+# profiles/r07/dw_held_serial_ab.jsonl)
+DW_HOLD_LAYERS = 4
+
+
+class Seg(NamedTuple):
+    """One parked reduction, a lasr_reduce_multi segment: the P rows of part [P, ncols] are summed
+    into out0 (added to it when accumulate), the columns from `split` on into out1."""
+
+    part: torch.Tensor
+    P: int
+    ncols: int
+    out0: torch.Tensor
+    out1: Optional[torch.Tensor]
+    split: int
+    accumulate: int
+
+    @classmethod
+    def of(cls, part, P, ncols, out0, out1=None, split=None, accumulate=True):
+        return cls(part, int(P), int(ncols), out0, out1, int(ncols if split is None else split), int(accumulate))
+
+
+class Refs(NamedTuple):
+    """What a queued GEMM keeps alive until it is launched: its operands, and where the launch or
+    a slab made later writes through them, its output and bias rowsum (else None)."""
+
+    a: Optional[torch.Tensor]
+    b: Optional[torch.Tensor]
+    c: Optional[torch.Tensor] = None
+    rowsum: Optional[torch.Tensor] = None
+
+
+class QueuedGemm(NamedTuple):
+    """A dW GEMM waiting for its lasr_gemm_dw_group launch.  key is its family, the problems that
+    may share a launch: the group tile (tm, tn), or DIRECT_FAMILY."""
+
+    key: object
+    args: N.GemmArgs
+    refs: Refs
+
+
+# family of the full-K direct problems (DW_DIRECT_MIN_TILES): 128 x 128 tiles, but never in a
+# launch with the split problems of that tile
+DIRECT_FAMILY = "direct"
+
+
+def _group_div(key):
+    """DW_GROUP_SPLIT_DIV of a group tile: a dict by tile, or one number for every tile."""
+    d = DW_GROUP_SPLIT_DIV
+    return max(1, d.get(key, 1) if isinstance(d, dict) else int(d))
+
+
+def _serial_tiles(key, M, Nn):
+    """Output tiles of a problem on its family's group tile (lasr_gemm_dw_group)."""
+    if key == (64, 64):
+        return -(-M // 64) * -(-Nn // 64)
+    if M >= 256 and Nn >= 256:
+        return -(-M // 256) * -(-Nn // 128)
+    return -(-M // 128) * -(-Nn // 128)
+
+
+def _dw_slab(sp, M, Nn, rowsum, device):
+    """The fp32 partials of a dW GEMM split sp ways, alive until their reduction: sp slabs of C,
+    then the rowsum partials (fused) or the column-sum scratch (unfused, fp32 operands)."""
+    nrs = (sp + 128) * M if rowsum is not None else 0
+    return torch.empty(sp * M * Nn + nrs, dtype=torch.float32, device=device)
+
+
+_PUSHED = {}  # library setter -> the last value pushed through it
+
+
+def _pushed(setter, value):
+    """Keep a library-side setting equal to its switch here: call the setter when the value changes."""
+    if _PUSHED.get(setter) != value:
+        N.call(setter, int(value))
+        _PUSHED[setter] = value
+
+
+def _launch_dw_groups(q, before_family=None):
+    """Launch queued dW GEMMs family by family, families in the order of their first problem,
+    <= _GROUP_MAX problems per lasr_gemm_dw_group launch.  before_family(key, problems, launches)
+    runs ahead of each family's launches.  The operand references die with q in the caller,
+    after the launches were enqueued."""
+    _pushed("lasr_gemm_dw_group_order", DW_GROUP_LPT)
+    families = {}
+    for g in q:
+        families.setdefault(g.key, []).append(g)
+    for key, fam in families.items():
+        chunks = [fam[i:i + _GROUP_MAX] for i in range(0, len(fam), _GROUP_MAX)]
+        if before_family is not None:
+            before_family(key, fam, chunks)
+        for ch in chunks:
+            arr = (N.GemmArgs * len(ch))(*[g.args for g in ch])
+            N.call("lasr_gemm_dw_group", arr, len(ch), stream())
+
+
+def _reduce(segs):
+    """One lasr_reduce_multi launch over the segments."""
+    arr = (N.ReduceSeg * len(segs))()
+    for i, s in enumerate(segs):
+        arr[i] = N.ReduceSeg(ptr(s.part), s.ncols, s.P, s.accumulate, ptr(s.out0), ptr(s.out1), s.split)
+    N.call("lasr_reduce_multi", arr, len(segs), stream())
+
+
+def _flush_node_end(segs):
+    """What the end of a backward node launches: its grouped dW GEMMs, then every reduction."""
+    if _DEFER.gemms:
+        _DEFER.flush_gemms()
+    if segs:
+        _reduce(segs)
+
+
 class _Deferred:
     """Parameter-gradient reductions parked until the end of a backward node: the
     partial-sum buffers of LayerNorm gamma/beta, the positional biases and the split-K
     weight gradients (+ their bias rowsums) are collected and finished by ONE
-    lasr_reduce_multi launch, with each reduction's usual summation order."""
+    lasr_reduce_multi launch, with each reduction's usual summation order.  The node's
+    grouped dW GEMMs are queued here too (kernels._queue_dw decides which list takes one)."""
 
     def __init__(self):
-        self.depth = 0
-        self.segs = []
-        self.gemms = []  # queued partials-only dW GEMMs: (tile key, args, operand refs)
-        self.held = []  # reductions of finished `hold` blocks, not yet launched
-        self.done = []  # their on_done callbacks, in block order
+        self.depth = 0  # open deferred_reductions blocks
         self.holding = False  # inside an outermost hold block
-        self.held_gemms = []  # dW GEMMs of finished `hold` blocks, not yet launched (no slab yet)
+        self.segs = []  # the open block's reductions (Seg)
+        self.gemms = []  # its dW GEMMs that launch at its end: slab made, or direct (QueuedGemm)
+        self.waiting = []  # its dW GEMMs that have no slab yet: they join held_gemms at its end
+        self.held = []  # reductions of finished hold blocks, not yet launched
+        self.held_gemms = []  # dW GEMMs of finished hold blocks, not yet launched (no slab yet)
         self.held_layers = 0  # hold blocks whose GEMMs wait in held_gemms
+        self.done = []  # on_done callbacks of the blocks in held, in block order
+
+    def enter(self, hold, on_done):
+        if self.depth and (hold or on_done is not None):
+            raise RuntimeError("deferred_reductions: hold / on_done inside another deferred block would be dropped")
+        if self.depth == 0:
+            self.holding = bool(hold)
+        self.depth += 1
+
+    def exit(self, hold, on_done, ok):
+        """End of a block (ok: without an exception).  An inner block leaves everything to the
+        outermost one, which queues its work (hold) or launches all that is queued."""
+        self.depth -= 1
+        if self.depth:
+            return
+        self.holding = False
+        waiting, self.waiting = self.waiting, []
+        if hold and ok:
+            if self.gemms:
+                self.flush_gemms()
+            self.held.extend(self.segs)
+            self.segs = []
+            if on_done is not None:
+                self.done.append(on_done)
+            if waiting:
+                self.held_gemms.extend(waiting)
+                self.held_layers += 1
+                if DW_HOLD_LAYERS and self.held_layers >= DW_HOLD_LAYERS:
+                    self.flush_held_gemms()
+        else:
+            # the block that ends the hold (a segment's lowest layer) adds its own GEMMs to
+            # the families it flushes; a raising block's are dropped here, unlaunched
+            if ok:
+                self.held_gemms.extend(waiting)
+            if on_done is not None:
+                self.done.append(on_done)
+            self.flush()
+
+    def defer(self, *segs):
+        self.segs.extend(segs)
+
+    def queue_gemm(self, key, args, refs, slab=True):
+        """Queue a dW GEMM (a copy of args) for a grouped launch: at the block's end, or
+        slab=False (no partial buffer yet) where the held reductions are flushed."""
+        (self.gemms if slab else self.waiting).append(QueuedGemm(key, N.GemmArgs.from_buffer_copy(args), refs))
+
+    def flush_gemms(self):
+        q, self.gemms = self.gemms, []
+        _launch_dw_groups(q)
+
+    def flush_held_gemms(self):
+        """Launch the hold blocks' waiting dW GEMMs, family by family in queue order."""
+        q, self.held_gemms = self.held_gemms, []
+        self.held_layers = 0
+        _launch_dw_groups(q, self._slabs_unless_serial)
+
+    def _slabs_unless_serial(self, key, fam, chunks):
+        """A held family runs serial-slice, without slabs, when its tiles fill the chip
+        (DW_SERIAL_MIN_TILES); else it takes the slab path: the partial buffers are made here
+        and reduced with the held reductions."""
+        tiles = [sum(_serial_tiles(key, g.args.M, g.args.N) for g in ch) for ch in chunks]
+        # (every launch but a family's last fills the chip; the 128 x 128 tile of an FFN-family
+        # problem narrower than 256 has no serial instance)
+        serial = (sum(tiles) >= DW_SERIAL_MIN_TILES and all(t >= DW_SERIAL_MIN_TILES for t in tiles[:-1])
+                  and (key == (64, 64) or all(g.args.M >= 256 and g.args.N >= 256 for g in fam)))
+        if serial:
+            return
+        for g in fam:
+            args, c, rowsum = g.args, g.refs.c, g.refs.rowsum
+            sp, M, Nn = -args.split_k, args.M, args.N
+            part = _dw_slab(sp, M, Nn, rowsum, c.device)
+            args.workspace, args.workspace_bytes = ptr(part), part.numel() * 4
+            self.held.append(Seg.of(part, sp, M * Nn, c, accumulate=args.beta == 1.0))
+            if rowsum is not None:
+                self.held.append(Seg.of(part[sp * M * Nn:], sp, M, rowsum))
+
+    def flush(self):
+        """Launch everything queued: the held GEMMs, the open block's, one reduction of all the
+        segments, then the callbacks in block order."""
+        if self.held_gemms:  # before the reductions: the slab families' segments join self.held
+            self.flush_held_gemms()
+        segs = self.held + self.segs
+        self.held, self.segs = [], []
+        done, self.done = self.done, []
+        if segs or self.gemms:
+            _flush_node_end(segs)
+        for fn in done:
+            fn()
+        # the partial buffers are released here; the caching allocator hands their memory only
+        # to work stream-ordered after the reduction
+
+    def held_count(self):
+        return len(self.held) + len(self.held_gemms)
 
 
 _DEFER = _Deferred()
@@ -96,202 +339,54 @@ def deferred_reductions(hold=False, on_done=None):
     grouped weight-gradient GEMMs wait too (DW_HOLD_GEMMS; their operands alive, so the caller
     must not modify them before that flush): they launch there, before the reductions, in
     queue order, and a family with enough tiles by then runs serial-slice, without slabs
-    (_flush_held_gemms).  A held block that raises drops its waiting GEMMs unlaunched.
+    (_Deferred.flush_held_gemms).  A held block that raises drops its waiting GEMMs unlaunched.
 
     Only an outermost block can hold or take a callback (its end is where reductions are
     launched or queued): asking for either inside another block raises."""
-    if _DEFER.depth and (hold or on_done is not None):
-        raise RuntimeError("deferred_reductions: hold / on_done inside another deferred block would be dropped")
-    if _DEFER.depth == 0:
-        _DEFER.holding = bool(hold)
-    _DEFER.depth += 1
+    _DEFER.enter(hold, on_done)
     ok = False
     try:
         yield
         ok = True
     finally:
-        _DEFER.depth -= 1
-        if _DEFER.depth == 0:
-            _DEFER.holding = False
-            waiting = [q for q in _DEFER.gemms if _waits(q)]
-            _DEFER.gemms = [q for q in _DEFER.gemms if not _waits(q)]
-            if hold and ok:
-                if _DEFER.gemms:
-                    _flush_gemm_group()
-                _DEFER.held.extend(_DEFER.segs)
-                _DEFER.segs = []
-                if on_done is not None:
-                    _DEFER.done.append(on_done)
-                if waiting:
-                    _DEFER.held_gemms.extend(waiting)
-                    _DEFER.held_layers += 1
-                    if DW_HOLD_LAYERS and _DEFER.held_layers >= DW_HOLD_LAYERS:
-                        _flush_held_gemms()
-            else:
-                # the block that ends the hold (a segment's lowest layer) adds its own GEMMs to
-                # the families it flushes; a raising block's are dropped here, unlaunched
-                if ok:
-                    _DEFER.held_gemms.extend(waiting)
-                if on_done is not None:
-                    _DEFER.done.append(on_done)
-                flush_reductions()
+        _DEFER.exit(hold, on_done, ok)
+
+
+def flush_reductions():
+    _DEFER.flush()
 
 
 def held_reductions():
     """Number of reductions and weight-gradient GEMMs queued by hold blocks and not yet launched."""
-    return len(_DEFER.held) + len(_DEFER.held_gemms)
+    return _DEFER.held_count()
 
 
-def _defer(part, P, Ncols, out0, out1=None, split=None, accumulate=True):
-    _DEFER.segs.append((part, int(P), int(Ncols), out0, out1, int(split if split is not None else Ncols),
-                        int(accumulate)))
+def _defer(part, P, ncols, out0, out1=None, split=None, accumulate=True):
+    _DEFER.defer(Seg.of(part, P, ncols, out0, out1, split, accumulate))
 
 
-# Grouped weight gradients: dW GEMMs marked group=True inside a deferred_reductions block are
-# queued and launched at its end, one lasr_gemm_dw_group launch per planned tile (<= 32
-# problems each), before the reductions (tests set DW_GROUP = False to compare with lone launches).
-DW_GROUP = True
-# plan tile -> group (lasr_gemm_dw_group runs the 64 x 128 / 128 x 64 plans, the FFN-sized
-# weights, on 128 x 128 tiles)
-_GROUP_TILES = {(64, 64): (64, 64), (64, 128): (128, 128), (128, 64): (128, 128)}
-# grouped problems fill the chip together: each takes 1/div of the K slices the planner gives
-# a lone launch (fewer fp32 partial slabs to write and reduce); 128 x 128 groups keep half
-# (DESIGN §4: the other divisors measured slower)
-DW_GROUP_SPLIT_DIV = {(64, 64): 4, (128, 128): 2}
-# Direct grouped weight gradients: FFN-sized problems with >= this many full-K 128 x 128 tiles
-# (the d 512 FFN weights: 64 each, a group of four = 256 tiles) skip the K split and write the
-# gradient itself (beta = 1), no fp32 partial slab to write and reduce.  Measured at config 4
-# (VERDICT r05 item 3): 20.13 -> 20.74 ms per step, the full-K 128 x 128 tiles are L2-feed bound
-# where the 256 x 128 split-2 tiles are not (profiles/r06/step_ab_dw_direct_large_rejected.jsonl,
-# DESIGN §4); 0 = off.  tests/test_kernels_gpu.py::test_gemm_dw_group_direct pins the path.
-DW_DIRECT_MIN_TILES = 0
+def _partials(nfloats, device, outlives):
+    """The fp32 buffer a kernel writes its partial sums to: a fresh one when it outlives the call
+    (parked for the block's reduction, or used beside the workspace), else the shared workspace."""
+    return torch.empty(nfloats, dtype=torch.float32, device=device) if outlives else WS.get(nfloats, device)
 
 
-# GEMMs whose 64 x 64 grid cannot fill half the chip and whose K is long are split over K
-# (lasr_gemm autosplit; the split-K reduction applies the epilogue).
-SMALL_GRID_SPLIT = True
-SMALL_GRID_TILES = 128  # (64 x 64 tiles below which a K >= 1024 GEMM is split)
-
-
-def _group_div(key):
-    d = DW_GROUP_SPLIT_DIV
-    return d.get(key, 1) if isinstance(d, dict) else d
-_GROUP_MAX = 32  # problems per lasr_gemm_dw_group launch (LASR_DW_GROUP_MAX)
-
-# Held weight-gradient GEMMs: inside a hold block the grouped dW GEMMs are queued without a
-# slab and launched where the held reductions are (tests set False to compare).
-DW_HOLD_GEMMS = True
-# A held family (one group tile) whose tiles at the flush fill the chip (>= the CU count) runs
-# serial-slice: one block per tile runs the planned K slices in order and writes the gradient
-# itself, the bits of slabs + lasr_reduce_multi (DESIGN §4).  Smaller families get their slabs
-# at the flush and take the slab path.  Counts only: the same on every step and rank.
-DW_SERIAL_MIN_TILES = 256
-# the waiting GEMMs are launched after this many hold blocks even inside a segment; 0 = at the
-# segment's end only.  4 layers of the small model are one full round of FFN tiles (256) and
-# measured best of 4 / 6 / whole segment on small, large and long (DESIGN §4,
-# profiles/r07/dw_held_serial_ab.jsonl)
-DW_HOLD_LAYERS = 4
-
-
-def _waits(q):
-    """A queued dW GEMM that has no slab yet (queued inside a hold block)."""
-    return q[1].split_k <= -2 and not q[1].workspace
-
-
-def _serial_tiles(key, M, Nn):
-    """Output tiles of a problem on its family's group tile (lasr_gemm_dw_group)."""
-    if key == (64, 64):
-        return -(-M // 64) * -(-Nn // 64)
-    if M >= 256 and Nn >= 256:
-        return -(-M // 256) * -(-Nn // 128)
-    return -(-M // 128) * -(-Nn // 128)
-
-
-def _flush_held_gemms():
-    """Launch the hold blocks' waiting dW GEMMs, family by family in queue order."""
-    q, _DEFER.held_gemms = _DEFER.held_gemms, []
-    _DEFER.held_layers = 0
-    _set_dw_order()
-    byt = {}
-    for key, args, refs in q:
-        byt.setdefault(key, []).append((args, refs))
-    for key, lst in byt.items():
-        chunks = [lst[i:i + _GROUP_MAX] for i in range(0, len(lst), _GROUP_MAX)]
-        tiles = [sum(_serial_tiles(key, a.M, a.N) for a, _ in ch) for ch in chunks]
-        # (every launch but a family's last fills the chip; the 128 x 128 tile of an FFN-family
-        # problem narrower than 256 has no serial instance)
-        serial = (sum(tiles) >= DW_SERIAL_MIN_TILES and all(t >= DW_SERIAL_MIN_TILES for t in tiles[:-1])
-                  and (key == (64, 64) or all(a.M >= 256 and a.N >= 256 for a, _ in lst)))
-        if not serial:
-            # the slab path: the partial buffers are made here and reduced with the held reductions
-            for args, (a, b, c, rowsum) in lst:
-                sp, M, Nn = -args.split_k, args.M, args.N
-                nrs = (sp + 128) * M if rowsum is not None else 0
-                part = torch.empty(sp * M * Nn + nrs, dtype=torch.float32, device=c.device)
-                args.workspace, args.workspace_bytes = ptr(part), part.numel() * 4
-                _DEFER.held.append((part, sp, M * Nn, c, None, M * Nn, int(args.beta == 1.0)))
-                if rowsum is not None:
-                    _DEFER.held.append((part[sp * M * Nn:], sp, M, rowsum, None, M, 1))
-        for ch in chunks:
-            arr = (N.GemmArgs * len(ch))(*[a for a, _ in ch])
-            N.call("lasr_gemm_dw_group", arr, len(ch), stream())
-    # the operand references in q die here, after the launches were enqueued
-
-
-# grouped dW blocks laid out longest K slice first (lasr_gemm_dw_group_order; same bits)
-DW_GROUP_LPT = True
-_dw_order_set = [None]
-
-
-def _set_dw_order():
-    if _dw_order_set[0] != DW_GROUP_LPT:
-        N.call("lasr_gemm_dw_group_order", int(DW_GROUP_LPT))
-        _dw_order_set[0] = DW_GROUP_LPT
-
-
-def _flush_gemm_group():
-    q, _DEFER.gemms = _DEFER.gemms, []
-    _set_dw_order()
-    byt = {}
-    for key, args, refs in q:
-        byt.setdefault(key, []).append(args)
-    for key, lst in byt.items():
-        for i in range(0, len(lst), _GROUP_MAX):
-            chunk = lst[i:i + _GROUP_MAX]
-            arr = (N.GemmArgs * len(chunk))(*chunk)
-            N.call("lasr_gemm_dw_group", arr, len(chunk), stream())
-    # the operand references in q die here, after the launches were enqueued
-
-
-def _flush_node_end(segs):
-    if _DEFER.gemms:
-        _flush_gemm_group()
-    if segs:
-        arr = (N.ReduceSeg * len(segs))()
-        for i, (part, P, Ncols, o0, o1, split, acc) in enumerate(segs):
-            arr[i] = N.ReduceSeg(ptr(part), Ncols, P, acc, ptr(o0), ptr(o1), split)
-        N.call("lasr_reduce_multi", arr, len(segs), stream())
-
-
-def flush_reductions():
-    if _DEFER.held_gemms:  # before the reductions: the slab families' segments join _DEFER.held
-        _flush_held_gemms()
-    segs = _DEFER.held + _DEFER.segs
-    _DEFER.held, _DEFER.segs = [], []
-    done, _DEFER.done = _DEFER.done, []
-    if segs or _DEFER.gemms:
-        _flush_node_end(segs)
-    for fn in done:
-        fn()
-    # the partial buffers are released here; the caching allocator hands their memory only
-    # to work stream-ordered after the reduction
-
+def _reduce_or_defer(*segs):
+    """Inside a deferred_reductions block park the segments for its reduction; outside one,
+    reduce them now, in one launch."""
+    if _DEFER.depth:
+        _DEFER.defer(*segs)
+    else:
+        _reduce(segs)
 
 
 # ----------------------------------------------------------------------- GEMM ---
 # the planner's 64 x 64 tiles for outputs at most 64 wide (lasr_gemm_narrow_tiles; same bits)
 GEMM_NARROW_TILES = True
-_narrow_set = [None]
+# GEMMs whose 64 x 64 grid cannot fill half the chip and whose K is long are split over K
+# (lasr_gemm autosplit; the split-K reduction applies the epilogue).
+SMALL_GRID_SPLIT = True
+SMALL_GRID_TILES = 128  # (64 x 64 tiles below which a K >= 1024 GEMM is split)
 
 
 def _split(t: torch.Tensor):
@@ -305,6 +400,135 @@ def _split(t: torch.Tensor):
     if nb == 1:
         return (st[0], 0), (sh[0], 1), st[1], st[2]
     return (st[0], st[1]), (sh[0], sh[1]), st[2], st[3]
+
+
+def _gemm_args(a, b, c):
+    """GemmArgs with the shapes, strides, pointers and dtypes of the logical views a (..,M,K),
+    b (..,K,N), c (..,M,N); marshalling only, the epilogue fields are the caller's."""
+    M, K = a.shape[-2], a.shape[-1]
+    K2, Nn = b.shape[-2], b.shape[-1]
+    assert K == K2 and c.shape[-2] == M and c.shape[-1] == Nn, (a.shape, b.shape, c.shape)
+    assert a.dtype == b.dtype
+    (sa1, sa2), (za1, za2), a_m, a_k = _split(a)
+    (sb1, sb2), (zb1, zb2), b_k, b_n = _split(b)
+    (sc1, sc2), (z1, z2), c_m, c_n = _split(c)
+    assert c_n == 1, "C must be row-contiguous"
+    assert (za1, za2) == (z1, z2) and (zb1, zb2) == (z1, z2), "batch shapes differ"
+    if a_k != 1 and a_m != 1:
+        raise ValueError("A needs a unit stride")
+    if b_k != 1 and b_n != 1:
+        raise ValueError("B needs a unit stride")
+    args = N.GemmArgs()
+    args.M, args.N, args.K = M, Nn, K
+    args.batch, args.batch_div = z1 * z2, z2
+    args.A, args.lda_m, args.lda_k, args.sa1, args.sa2 = ptr(a), a_m, a_k, sa1, sa2
+    # B logical [K,N]: kernel wants ldb_n (stride along n) and ldb_k (stride along k)
+    args.B, args.ldb_n, args.ldb_k, args.sb1, args.sb2 = ptr(b), b_n, b_k, sb1, sb2
+    args.C, args.ldc, args.sc1, args.sc2 = ptr(c), c_m, sc1, sc2
+    if a_k == 1 and a_m == 1:
+        args.lda_k = 1
+    if b_k == 1 and b_n == 1:
+        args.ldb_k = 1
+    args.in_dtype, args.c_dtype = dt(a), dt(c)
+    return args
+
+
+def _auto_split(a, M, Nn, K, batch, split_k, rowsum, zout, group):
+    """Small grid, long K (the decoder's B*(L+1)-row GEMMs): split K, reduce with the epilogue."""
+    return (split_k == 1 and SMALL_GRID_SPLIT and rowsum is None and zout is None and not group
+            and a.dtype == torch.bfloat16 and batch == 1 and K >= 1024
+            and ((M + 63) // 64) * ((Nn + 63) // 64) < SMALL_GRID_TILES)
+
+
+def _plan(args):
+    """(tile_m, tile_n, K slices, LASR_PLAN_* bits) lasr_gemm would use; nothing is launched."""
+    tm, tn, sp, fl = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    N.call("lasr_gemm_plan", C.byref(args), C.byref(tm), C.byref(tn), C.byref(sp), C.byref(fl))
+    return tm.value, tn.value, sp.value, fl.value
+
+
+def _queue_dw(args, a, b, c, rowsum, group):
+    """A split-K weight gradient inside a deferred_reductions block (the caller checked: split_k=0
+    asked for, no epilogue but beta 0 / 1, one contiguous fp32 C): its reduction, and the launch of
+    a grouped one, wait for the block's end.  False: the plan does not split K, launch it as usual."""
+    M, Nn = args.M, args.N
+    tm, tn, sp, fl = _plan(args)
+    grouped = (group and DW_GROUP and (tm, tn) in _GROUP_TILES and (fl & 1) and args.lda_m == 1 and args.ldb_n == 1
+               and a.dtype == torch.bfloat16)
+    if (grouped and DW_DIRECT_MIN_TILES > 0 and _GROUP_TILES[(tm, tn)] == (128, 128)
+            and ((M + 127) // 128) * ((Nn + 127) // 128) >= DW_DIRECT_MIN_TILES):
+        # full-K direct problem of the group: C itself (beta 0 / 1), its bias rowsum direct
+        args.split_k = 1
+        args.workspace, args.workspace_bytes = None, 0
+        _DEFER.queue_gemm(DIRECT_FAMILY, args, Refs(a, b, c, rowsum))
+        return True
+    div = _group_div(_GROUP_TILES[(tm, tn)]) if grouped else 1
+    if grouped and (div > 1 or sp < 2):
+        # short K too (the positional-projection weight, K = T'): two slices join the group
+        sp = max(2, sp // div)
+        args.split_k = -sp
+        tm, tn, _, fl = _plan(args)
+        grouped = (tm, tn) in _GROUP_TILES and bool(fl & 1)
+    if sp <= 1:
+        return False
+    # the explicit slice count from here on: a slab is sized for sp slices, and a re-derived
+    # auto split (-1) could differ from sp after the group adjustment
+    args.split_k = -sp
+    if (grouped and (_DEFER.holding or _DEFER.held_gemms) and DW_HOLD_GEMMS and sp <= 64
+            and (M * Nn) % 4 == 0 and (rowsum is None or (M % 4 == 0 and fl & 2))):
+        # a hold block, or the block that ends the hold: the GEMM waits, without a slab, for the
+        # flush of the held reductions (_Deferred.flush_held_gemms: serial-slice, or the slab path
+        # with the slab made there).  The shapes kept out are those whose reduction is not
+        # lasr_reduce_multi's slice-order sum.
+        args.workspace, args.workspace_bytes = None, 0
+        _DEFER.queue_gemm(_GROUP_TILES[(tm, tn)], args, Refs(a, b, c, rowsum), slab=False)
+        return True
+    # partials-only launch (split_k < 0) into a buffer that lives until the flush
+    part = _dw_slab(sp, M, Nn, rowsum, c.device)
+    args.workspace, args.workspace_bytes = ptr(part), part.numel() * 4
+    if grouped:
+        _DEFER.queue_gemm(_GROUP_TILES[(tm, tn)], args, Refs(a, b))
+    else:
+        N.call("lasr_gemm", C.byref(args), stream())
+    _defer(part, sp, M * Nn, c, accumulate=args.beta == 1.0)
+    if rowsum is not None and fl & 2:  # LASR_PLAN_ROWSUM_FUSED: partials follow C's
+        _defer(part[sp * M * Nn:], sp, M, rowsum)
+    return True
+
+
+def _gemm_ln_fwd(args, c, rowsum, ln_fwd):
+    """lasr_gemm_ln_fwd: the GEMM, then the LayerNorm of c's rows."""
+    g_, b_, eps, y, mean, rstd = ln_fwd
+    assert c.dtype == torch.float32 and c.is_contiguous() and args.batch == 1 and rowsum is None
+    N.call("lasr_gemm_ln_fwd", C.byref(args), ptr(g_), ptr(b_), float(eps), ptr(y), dt(y), ptr(mean), ptr(rstd),
+           stream())
+
+
+def _gemm_qbias_bwd(args, c, qbias):
+    """lasr_gemm_qbias_bwd: the GEMM with qbias_bwd's blocks beside its split-K reduction."""
+    dqu, dqv, B_, T_, H_, dk_, dqkv, du, dv = qbias
+    assert c.dtype == dqu.dtype == dqv.dtype == dqkv.dtype
+    D_ = H_ * dk_
+    nchunk = (B_ * T_ + 63) // 64  # QB_ROWS (csrc/qbias.h)
+    part = _partials(nchunk * 2 * D_, c.device, outlives=True)  # (the GEMM's split-K partials live in WS)
+    N.call("lasr_gemm_qbias_bwd", C.byref(args), ptr(dqu), ptr(dqv), dt(dqu), B_, T_, H_, dk_, ptr(dqkv),
+           dqkv.stride(0), ptr(part), part.numel(), stream())
+    _reduce_or_defer(Seg.of(part, nchunk, 2 * D_, du, dv, split=D_))
+
+
+def _gemm_ln_bwd(args, c, rowsum, q):
+    """lasr_gemm_ln_bwd: the GEMM, then the LayerNorm backward of c = dln."""
+    assert c.is_contiguous() and args.batch == 1 and rowsum is None
+    M, Nn = args.M, args.N
+    nblk = (M + 15) // 16  # lasr_layernorm_bwd's 16-row blocks
+    # (its own buffer: the GEMM's split-K partials live in WS)
+    part = _partials(nblk * 2 * Nn, c.device, outlives=True)
+    N.call("lasr_gemm_ln_bwd", C.byref(args), ptr(q.x), dt(q.x), ptr(q.g), ptr(q.mean), ptr(q.rstd),
+           ptr(q.dres), dt(q.dres) if q.dres is not None else 0, ptr(q.dx), dt(q.dx), ptr(part), part.numel(),
+           ptr(q.gb), dt(q.gb) if q.gb is not None else 0, float(q.bscale), float(q.bp), int(q.bseed), stream())
+    if q.dgamma is not None or q.dbeta is not None:
+        assert q.dgamma is not None and q.dbeta is not None
+        _reduce_or_defer(Seg.of(part, nblk, 2 * Nn, q.dgamma, q.dbeta, split=Nn))
 
 
 def gemm(
@@ -353,36 +577,12 @@ def gemm(
     object with x, g, mean, rstd, dx, dgamma, dbeta, dres, gb, bscale, bp, bseed): the
     LayerNorm backward of c = dln follows (lasr_gemm_ln_bwd), its dgamma / dbeta partials
     deferred or reduced like layernorm_bwd's.  qbias=(dqu, dqv, B, T, H, dk, dqkv, du, dv):
-    qbias_bwd's work runs beside this GEMM's split-K reduction (lasr_gemm_qbias_bwd)."""
-    if _narrow_set[0] != GEMM_NARROW_TILES:
-        N.call("lasr_gemm_narrow_tiles", int(GEMM_NARROW_TILES))
-        _narrow_set[0] = GEMM_NARROW_TILES
-    M, K = a.shape[-2], a.shape[-1]
-    K2, Nn = b.shape[-2], b.shape[-1]
-    assert K == K2 and c.shape[-2] == M and c.shape[-1] == Nn, (a.shape, b.shape, c.shape)
-    assert a.dtype == b.dtype
-    (sa1, sa2), (za1, za2), a_m, a_k = _split(a)
-    (sb1, sb2), (zb1, zb2), b_k, b_n = _split(b)
-    (sc1, sc2), (zc1, zc2), c_m, c_n = _split(c)
-    assert c_n == 1, "C must be row-contiguous"
-    z1, z2 = zc1, zc2
-    assert (za1, za2) == (z1, z2) and (zb1, zb2) == (z1, z2), "batch shapes differ"
-    if a_k != 1 and a_m != 1:
-        raise ValueError("A needs a unit stride")
-    if b_k != 1 and b_n != 1:
-        raise ValueError("B needs a unit stride")
-    args = N.GemmArgs()
-    args.M, args.N, args.K = M, Nn, K
-    args.batch, args.batch_div = z1 * z2, z2
-    args.A, args.lda_m, args.lda_k, args.sa1, args.sa2 = ptr(a), a_m, a_k, sa1, sa2
-    # B logical [K,N]: kernel wants ldb_n (stride along n) and ldb_k (stride along k)
-    args.B, args.ldb_n, args.ldb_k, args.sb1, args.sb2 = ptr(b), b_n, b_k, sb1, sb2
-    args.C, args.ldc, args.sc1, args.sc2 = ptr(c), c_m, sc1, sc2
-    if a_k == 1 and a_m == 1:
-        args.lda_k = 1
-    if b_k == 1 and b_n == 1:
-        args.ldb_k = 1
-    args.in_dtype, args.c_dtype = dt(a), dt(c)
+    qbias_bwd's work runs beside this GEMM's split-K reduction (lasr_gemm_qbias_bwd).
+
+    plan_only: nothing is launched; returns the plan (tile_m, tile_n, K slices, LASR_PLAN_* bits)."""
+    _pushed("lasr_gemm_narrow_tiles", GEMM_NARROW_TILES)
+    args = _gemm_args(a, b, c)
+    M, Nn, K, batch = args.M, args.N, args.K, args.batch
     args.alpha, args.alpha_dev, args.beta = alpha, ptr(alpha_dev), beta
     args.bias = ptr(bias)
     args.act = act
@@ -396,125 +596,43 @@ def gemm(
     args.ksub = int(ksub)
     if res is not None:
         args.res, args.res_dtype, args.ldres, args.res_scale = ptr(res), dt(res), res.stride(0), res_scale
-    auto_split = (split_k == 1 and SMALL_GRID_SPLIT and rowsum is None and zout is None and not group
-                  and a.dtype == torch.bfloat16 and z1 * z2 == 1 and K >= 1024
-                  and ((M + 63) // 64) * ((Nn + 63) // 64) < SMALL_GRID_TILES)
-    if auto_split:  # small grid, long K (the decoder's B*(L+1)-row GEMMs): split K, reduce with the epilogue
+    auto_split = _auto_split(a, M, Nn, K, batch, split_k, rowsum, zout, group)
+    if auto_split:
         split_k = 0
     args.split_k = split_k
     if rowsum is not None:
         # fused bias gradient rowsum[m] += sum_k a[m, k] (fp32, a M-contiguous)
         assert rowsum.dtype == torch.float32 and rowsum.is_contiguous() and rowsum.numel() == M
-        assert z1 * z2 == 1 and a_m == 1, "rowsum needs batch 1 and an M-contiguous A"
+        assert batch == 1 and args.lda_m == 1, "rowsum needs batch 1 and an M-contiguous A"
         args.rowsum = ptr(rowsum)
     if split_k != 1 or rowsum is not None:
         ns = 64 if split_k <= 0 else split_k
-        need = ns * z1 * z2 * M * Nn + (ns + 128) * M if rowsum is not None else ns * z1 * z2 * M * Nn
+        need = ns * batch * M * Nn + (ns + 128) * M if rowsum is not None else ns * batch * M * Nn
         ws = WS.get(need, c.device)
         args.workspace, args.workspace_bytes = ptr(ws), ws.numel() * 4
     if plan_only:
-        tm, tn, sp, fl = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-        N.call("lasr_gemm_plan", C.byref(args), C.byref(tm), C.byref(tn), C.byref(sp), C.byref(fl))
-        if plan_only == "flags":
-            return tm.value, tn.value, sp.value, fl.value
-        return tm.value, tn.value, sp.value
+        return _plan(args)
     if (_DEFER.depth and split_k == 0 and not auto_split and beta in (0.0, 1.0) and alpha == 1.0 and alpha_dev is None
             and bias is None and act == N.ACT_NONE and zout is None and aux is None and res is None
-            and drop_p <= 0.0 and z1 * z2 == 1 and c.dtype == torch.float32 and c.is_contiguous()):
-        tm, tn, sp, fl = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-        N.call("lasr_gemm_plan", C.byref(args), C.byref(tm), C.byref(tn), C.byref(sp), C.byref(fl))
-        sp = sp.value
-        grouped = (group and DW_GROUP and (tm.value, tn.value) in _GROUP_TILES
-                   and (fl.value & 1) and a_m == 1 and b_n == 1 and a.dtype == torch.bfloat16)
-        if (grouped and DW_DIRECT_MIN_TILES > 0 and _GROUP_TILES[(tm.value, tn.value)] == (128, 128)
-                and ((M + 127) // 128) * ((Nn + 127) // 128) >= DW_DIRECT_MIN_TILES):
-            # full-K direct problem of the group: C itself (beta 0 / 1), its bias rowsum direct
-            args.split_k = 1
-            args.workspace, args.workspace_bytes = None, 0
-            _DEFER.gemms.append(((128, 128, "direct"), N.GemmArgs.from_buffer_copy(args), (a, b, c, rowsum)))
-            return c
-        div = _group_div(_GROUP_TILES[(tm.value, tn.value)]) if grouped else 1
-        if grouped and (div > 1 or sp < 2):
-            # short K too (the positional-projection weight, K = T'): two slices join the group
-            sp = max(2, sp // max(1, div))
-            args.split_k = -sp
-            N.call("lasr_gemm_plan", C.byref(args), C.byref(tm), C.byref(tn), C.byref(C.c_int()), C.byref(fl))
-            grouped = (tm.value, tn.value) in _GROUP_TILES and bool(fl.value & 1)
-        if (sp > 1 and grouped and (_DEFER.holding or _DEFER.held_gemms) and DW_HOLD_GEMMS and sp <= 64
-                and (M * Nn) % 4 == 0 and (rowsum is None or (M % 4 == 0 and fl.value & 2))):
-            # a hold block: the GEMM waits, without a slab, for the flush of the held reductions
-            # (_flush_held_gemms: serial-slice, or the slab path with the slab made there).  The
-            # shapes kept out are those whose reduction is not lasr_reduce_multi's slice-order sum.
-            args.split_k = -sp
-            args.workspace, args.workspace_bytes = None, 0
-            key = _GROUP_TILES[(tm.value, tn.value)]
-            _DEFER.gemms.append((key, N.GemmArgs.from_buffer_copy(args), (a, b, c, rowsum)))
-            return c
-        if sp > 1:
-            # partials-only launch (split_k = -1) into a buffer that lives until the flush
-            # rowsum partials (fused) or the column-sum scratch (unfused, fp32 operands)
-            nrs = (sp + 128) * M if rowsum is not None else 0
-            part = torch.empty(sp * M * Nn + nrs, dtype=torch.float32, device=c.device)
-            # the explicit slice count on both paths: `part` is sized for sp slices, and a
-            # re-derived auto split (-1) could differ from sp after the group adjustment
-            args.split_k = -sp
-            args.workspace, args.workspace_bytes = ptr(part), part.numel() * 4
-            if grouped:
-                key = _GROUP_TILES[(tm.value, tn.value)]
-                _DEFER.gemms.append((key, N.GemmArgs.from_buffer_copy(args), (a, b)))
-            else:
-                N.call("lasr_gemm", C.byref(args), stream())
-            _defer(part, sp, M * Nn, c, accumulate=beta == 1.0)
-            if rowsum is not None and fl.value & 2:  # LASR_PLAN_ROWSUM_FUSED: partials follow C's
-                _defer(part[sp * M * Nn:], sp, M, rowsum)
-            return c
+            and drop_p <= 0.0 and batch == 1 and c.dtype == torch.float32 and c.is_contiguous()
+            and _queue_dw(args, a, b, c, rowsum, group)):
+        return c  # (a weight gradient whose reduction, or launch too, waits for the block's end)
     if ln_fwd is not None:
-        g_, b_, eps, y, mean, rstd = ln_fwd
-        assert c.dtype == torch.float32 and c.is_contiguous() and z1 * z2 == 1 and rowsum is None
-        N.call("lasr_gemm_ln_fwd", C.byref(args), ptr(g_), ptr(b_), float(eps), ptr(y), dt(y), ptr(mean), ptr(rstd),
-               stream())
-        return c
-    if qbias is not None:
-        dqu, dqv, B_, T_, H_, dk_, dqkv, du, dv = qbias
-        assert c.dtype == dqu.dtype == dqv.dtype == dqkv.dtype
-        D_ = H_ * dk_
-        nchunk = (B_ * T_ + 63) // 64  # QB_ROWS (qbias.h)
-        part = torch.empty(nchunk * 2 * D_, dtype=torch.float32, device=c.device)
-        N.call("lasr_gemm_qbias_bwd", C.byref(args), ptr(dqu), ptr(dqv), dt(dqu), B_, T_, H_, dk_, ptr(dqkv),
-               dqkv.stride(0), ptr(part), part.numel(), stream())
-        if _DEFER.depth:
-            _defer(part, nchunk, 2 * D_, du, dv, split=D_)
-        else:
-            arr = (N.ReduceSeg * 1)()
-            arr[0] = N.ReduceSeg(ptr(part), 2 * D_, nchunk, 1, ptr(du), ptr(dv), D_)
-            N.call("lasr_reduce_multi", arr, 1, stream())
-        return c
-    if ln_bwd is not None:
-        q = ln_bwd
-        assert c.is_contiguous() and z1 * z2 == 1 and rowsum is None
-        nblk = (M + 15) // 16  # lasr_layernorm_bwd's 16-row blocks
-        defer = _DEFER.depth and q.dgamma is not None and q.dbeta is not None
-        # (its own buffer: the GEMM's split-K partials live in WS)
-        part = torch.empty(nblk * 2 * Nn, dtype=torch.float32, device=c.device)
-        N.call("lasr_gemm_ln_bwd", C.byref(args), ptr(q.x), dt(q.x), ptr(q.g), ptr(q.mean), ptr(q.rstd),
-               ptr(q.dres), dt(q.dres) if q.dres is not None else 0, ptr(q.dx), dt(q.dx), ptr(part), part.numel(),
-               ptr(q.gb), dt(q.gb) if q.gb is not None else 0, float(q.bscale), float(q.bp), int(q.bseed), stream())
-        if defer:
-            _defer(part, nblk, 2 * Nn, q.dgamma, q.dbeta, split=Nn)
-        elif q.dgamma is not None or q.dbeta is not None:
-            assert q.dgamma is not None and q.dbeta is not None
-            arr = (N.ReduceSeg * 1)()
-            arr[0] = N.ReduceSeg(ptr(part), 2 * Nn, nblk, 1, ptr(q.dgamma), ptr(q.dbeta), Nn)
-            N.call("lasr_reduce_multi", arr, 1, stream())
-        return c
-    N.call("lasr_gemm", C.byref(args), stream())
+        _gemm_ln_fwd(args, c, rowsum, ln_fwd)
+    elif qbias is not None:
+        _gemm_qbias_bwd(args, c, qbias)
+    elif ln_bwd is not None:
+        _gemm_ln_bwd(args, c, rowsum, ln_bwd)
+    else:
+        N.call("lasr_gemm", C.byref(args), stream())
     return c
 
 
 def gemm_plan(a, b, c, flags=False, **kw):
     """(tile_m, tile_n, split_k) lasr_gemm would use for this call (nothing is launched);
     flags=True appends the LASR_PLAN_* bits (LDS-DMA path, fused rowsum, 64-deep stages)."""
-    return gemm(a, b, c, plan_only="flags" if flags else True, **kw)
+    plan = gemm(a, b, c, plan_only=True, **kw)
+    return plan if flags else plan[:3]
 
 
 def linear(x, w, out, bias=None, **kw):
@@ -555,12 +673,8 @@ def layernorm_bwd(x, dy, gamma, mean, rstd, dx, dgamma, dbeta, dres=None, gb=Non
     rows, D = x.shape
     nblk = (rows + 15) // 16  # LN_ROWS_PER_BLOCK (norm.hip)
     defer = _DEFER.depth and dgamma is not None and dbeta is not None
-    if defer:
-        ws = torch.empty(nblk * 2 * D, dtype=torch.float32, device=x.device)
-        og, ob = None, None
-    else:
-        ws = WS.get(nblk * 2 * D, x.device)
-        og, ob = dgamma, dbeta
+    ws = _partials(nblk * 2 * D, x.device, outlives=defer)
+    og, ob = (None, None) if defer else (dgamma, dbeta)  # (not deferred: the kernel reduces into them)
     N.call("lasr_layernorm_bwd", ptr(x), dt(x), ptr(dy), dt(dy), rows, D, ptr(gamma), ptr(mean),
            ptr(rstd), ptr(dres), dt(dres) if dres is not None else 0, ptr(dx), dt(dx),
            ptr(og), ptr(ob), ptr(ws), ws.numel(), ptr(gb),
@@ -578,19 +692,14 @@ def layernorm2_bwd(x1, dy1, dres1, g1, mean1, rstd1, dgamma1, dbeta1, x2, g2, me
     assert x1.dtype == x2.dtype == dres1.dtype == dx2.dtype == torch.float32
     assert dy1.shape == x1.shape == x2.shape == dres1.shape == dx2.shape
     nblk = (rows + 15) // 16  # LN_ROWS_PER_BLOCK (norm.hip)
-    part1 = torch.empty(nblk * 2 * D, dtype=torch.float32, device=x1.device)
-    part2 = torch.empty(nblk * 2 * D, dtype=torch.float32, device=x1.device)
+    # (two buffers alive at once: not the one workspace)
+    part1 = _partials(nblk * 2 * D, x1.device, outlives=True)
+    part2 = _partials(nblk * 2 * D, x1.device, outlives=True)
     N.call("lasr_layernorm2_bwd", ptr(x1), ptr(dy1), dt(dy1), ptr(dres1), rows, D, ptr(g1), ptr(mean1), ptr(rstd1),
            ptr(part1), ptr(x2), ptr(g2), ptr(mean2), ptr(rstd2), ptr(dx2), ptr(part2), ptr(gb2),
            dt(gb2) if gb2 is not None else 0, bscale, bp, bseed, stream())
-    if _DEFER.depth:
-        _defer(part1, nblk, 2 * D, dgamma1, dbeta1, split=D)
-        _defer(part2, nblk, 2 * D, dgamma2, dbeta2, split=D)
-        return
-    arr = (N.ReduceSeg * 2)()
-    arr[0] = N.ReduceSeg(ptr(part1), 2 * D, nblk, 1, ptr(dgamma1), ptr(dbeta1), D)
-    arr[1] = N.ReduceSeg(ptr(part2), 2 * D, nblk, 1, ptr(dgamma2), ptr(dbeta2), D)
-    N.call("lasr_reduce_multi", arr, 2, stream())
+    _reduce_or_defer(Seg.of(part1, nblk, 2 * D, dgamma1, dbeta1, split=D),
+                     Seg.of(part2, nblk, 2 * D, dgamma2, dbeta2, split=D))
 
 
 # ------------------------------------------------- full-row GEMM + LayerNorm ---
@@ -650,8 +759,7 @@ def linear_dx_ln_bwd(dy, w, x, gamma, mean, rstd, dx, dgamma, dbeta, dres=None, 
     D = w.shape[1]
     nblk = (M + 15) // 16
     defer = _DEFER.depth and dgamma is not None and dbeta is not None
-    part = torch.empty(nblk * 2 * D, dtype=torch.float32, device=dy.device) if defer else \
-        WS.get(nblk * 2 * D, dy.device)
+    part = _partials(nblk * 2 * D, dy.device, outlives=defer)
     a = N.RowLnArgs()
     a.M, a.D, a.K = M, D, Kd
     a.A, a.lda, a.W, a.ldw = ptr(dy), dy.stride(0), ptr(w), w.stride(0)
@@ -734,16 +842,14 @@ def qbias_fwd(qkv, B, T, H, dk, bu, bv, qu, qv):
 def qbias_bwd(dqu, dqv, B, T, H, dk, dqkv, du, dv):
     rows = B * T
     D = H * dk
-    nchunk = (rows + 63) // 64  # QB_ROWS (attn.hip)
-    if _DEFER.depth:
-        ws = torch.empty(nchunk * 2 * D, dtype=torch.float32, device=dqu.device)
-        N.call("lasr_qbias_bwd", ptr(dqu), ptr(dqv), dt(dqu), B, T, H, dk, ptr(dqkv), dqkv.stride(0),
-               None, None, ptr(ws), ws.numel(), stream())
-        _defer(ws, nchunk, 2 * D, du, dv, split=D)
-        return
-    ws = WS.get(nchunk * 2 * D, dqu.device)
+    nchunk = (rows + 63) // 64  # QB_ROWS (csrc/qbias.h)
+    defer = bool(_DEFER.depth)
+    ws = _partials(nchunk * 2 * D, dqu.device, outlives=defer)
+    ou, ov = (None, None) if defer else (du, dv)  # (not deferred: the kernel reduces into them)
     N.call("lasr_qbias_bwd", ptr(dqu), ptr(dqv), dt(dqu), B, T, H, dk, ptr(dqkv), dqkv.stride(0),
-           ptr(du), ptr(dv), ptr(ws), ws.numel(), stream())
+           ptr(ou), ptr(ov), ptr(ws), ws.numel(), stream())
+    if defer:
+        _defer(ws, nchunk, 2 * D, du, dv, split=D)
 
 
 def attn_softmax_fwd(s_ac, s_bd, B, H, Tq, Tk, ldS, mask, msb, msq, P, drop_p=0.0, seed=0,
@@ -994,18 +1100,23 @@ def bn_act_bwd(y, dh, scale, shift, mean, rstd, gamma, dgamma, dbeta, dy, batch_
            ws.numel(), int(bool(batch_stats)), act, stream())
 
 
+def _dwconv_partials(nparts, K, Cc, device, dw, db):
+    """(partials buffer, dw and db as the kernel gets them) of the depthwise backwards.  Deferred:
+    nparts rows of [C*K + C] parked for the block's reduction, no outputs; else the workspace,
+    one row more, and the kernel reduces into dw / db."""
+    if _DEFER.depth:
+        return _partials(nparts * (K + 1) * Cc, device, outlives=True), None, None
+    return _partials((nparts + 1) * (K + 1) * Cc, device, outlives=False), dw, db
+
+
 def glu_dwconv_bwd(z1, dy, B, T, Cc, K, w, dz1, dw, db):
     """dw [C, K] and db [C] accumulate; partials are [nparts][C*K + C] in their layout."""
     nparts = dwconv_nparts(B, T)
-    if _DEFER.depth:
-        ws = torch.empty(nparts * (K + 1) * Cc, dtype=torch.float32, device=z1.device)
-        N.call("lasr_glu_dwconv_bwd", ptr(z1), dt(z1), ptr(dy), dt(dy), B, T, Cc, K, ptr(w), ptr(dz1),
-               None, None, ptr(ws), ws.numel(), stream())
-        _defer(ws, nparts, (K + 1) * Cc, dw, db, split=K * Cc)
-        return
-    ws = WS.get((nparts + 1) * (K + 1) * Cc, z1.device)
+    ws, ow, ob = _dwconv_partials(nparts, K, Cc, z1.device, dw, db)
     N.call("lasr_glu_dwconv_bwd", ptr(z1), dt(z1), ptr(dy), dt(dy), B, T, Cc, K, ptr(w), ptr(dz1),
-           ptr(dw), ptr(db), ptr(ws), ws.numel(), stream())
+           ptr(ow), ptr(ob), ptr(ws), ws.numel(), stream())
+    if _DEFER.depth:
+        _defer(ws, nparts, (K + 1) * Cc, dw, db, split=K * Cc)
 
 
 def bn_act_glu_dwconv_bwd(y, dh, scale, shift, mean, rstd, gamma, dgamma, dbeta, z1, B, T, Cc, K, w, dz1, dw, db,
@@ -1015,18 +1126,14 @@ def bn_act_glu_dwconv_bwd(y, dh, scale, shift, mean, rstd, gamma, dgamma, dbeta,
     rows = y.shape[0]
     assert rows == B * T and y.shape[1] == Cc and dh.shape == y.shape and z1.shape == (rows, 2 * Cc)
     # (its own buffer: the depthwise partials below may take WS)
-    bn_ws = torch.empty(((rows + 63) // 64 + 1) * 2 * Cc, dtype=torch.float32, device=y.device)
+    bn_ws = _partials(((rows + 63) // 64 + 1) * 2 * Cc, y.device, outlives=True)
     nparts = dwconv_nparts(B, T)
-    head = (ptr(y), dt(y), ptr(dh), dt(dh), B, T, Cc, ptr(scale), ptr(shift), ptr(mean), ptr(rstd), ptr(gamma),
-            ptr(dgamma), ptr(dbeta), ptr(bn_ws), bn_ws.numel(), int(bool(batch_stats)), act, ptr(z1), dt(z1), K,
-            ptr(w), ptr(dz1))
+    ws, ow, ob = _dwconv_partials(nparts, K, Cc, z1.device, dw, db)
+    N.call("lasr_bn_act_glu_dwconv_bwd", ptr(y), dt(y), ptr(dh), dt(dh), B, T, Cc, ptr(scale), ptr(shift), ptr(mean),
+           ptr(rstd), ptr(gamma), ptr(dgamma), ptr(dbeta), ptr(bn_ws), bn_ws.numel(), int(bool(batch_stats)), act,
+           ptr(z1), dt(z1), K, ptr(w), ptr(dz1), ptr(ow), ptr(ob), ptr(ws), ws.numel(), stream())
     if _DEFER.depth:
-        ws = torch.empty(nparts * (K + 1) * Cc, dtype=torch.float32, device=z1.device)
-        N.call("lasr_bn_act_glu_dwconv_bwd", *head, None, None, ptr(ws), ws.numel(), stream())
         _defer(ws, nparts, (K + 1) * Cc, dw, db, split=K * Cc)
-        return
-    ws = WS.get((nparts + 1) * (K + 1) * Cc, z1.device)
-    N.call("lasr_bn_act_glu_dwconv_bwd", *head, ptr(dw), ptr(db), ptr(ws), ws.numel(), stream())
 
 
 # ---------------------------------------------------------------- elementwise ---

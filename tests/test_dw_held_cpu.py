@@ -1,5 +1,5 @@
 """Host-side order of the held weight-gradient GEMMs (kernels.deferred_reductions(hold=True),
-kernels._flush_held_gemms) with the native calls recorded: no GPU, no library call."""
+kernels._Deferred.flush_held_gemms) with the native calls recorded: no GPU, no library call."""
 
 import os
 import sys
@@ -31,7 +31,7 @@ def rec(monkeypatch):
     monkeypatch.setattr(K.N, "call", call)
     monkeypatch.setattr(K, "stream", lambda: 0)
     monkeypatch.setattr(K, "_DEFER", K._Deferred())
-    monkeypatch.setattr(K, "_dw_order_set", [K.DW_GROUP_LPT])
+    monkeypatch.setattr(K, "_PUSHED", {"lasr_gemm_dw_group_order": K.DW_GROUP_LPT})
     monkeypatch.setattr(K, "DW_HOLD_LAYERS", 0)  # (the hold-depth test sets its own)
     return K, calls
 
@@ -41,7 +41,7 @@ def _queue(K, key, M, Nn, sp=4, rowsum=False):
     a = K.N.GemmArgs()
     a.M, a.N, a.K, a.split_k, a.beta = M, Nn, 4096, -sp, 1.0
     c = torch.zeros(M, Nn)
-    K._DEFER.gemms.append((key, a, (None, None, c, torch.zeros(M) if rowsum else None)))
+    K._DEFER.waiting.append(K.QueuedGemm(key, a, K.Refs(None, None, c, torch.zeros(M) if rowsum else None)))
 
 
 def test_held_gemms_launch_before_held_reductions_in_queue_order(rec):

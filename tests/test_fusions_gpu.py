@@ -104,7 +104,7 @@ def test_dw_group_longest_slice_first(monkeypatch, d, heads):
     monkeypatch.setattr(K, "DW_GROUP_LPT", False)
     off = _step(cfg, B=8, T=1000, L=12)
     monkeypatch.setattr(K, "DW_GROUP_LPT", True)
-    K._flush_gemm_group()  # (restores the library's setting for the tests after this one)
+    K._pushed("lasr_gemm_dw_group_order", K.DW_GROUP_LPT)  # (restores the library's setting for the tests after this one)
     _same(on, off)
 
 

@@ -329,7 +329,7 @@ def test_gemm_dw_group_direct(R, monkeypatch):
                 res.append((dw, db))
             if grouped:
                 keys = {k for k, _, _ in kn._DEFER.gemms}
-                assert keys == {(128, 128, "direct")}, keys
+                assert keys == {kn.DIRECT_FAMILY}, keys
             assert not kn._DEFER.segs  # no partial slab to reduce
         torch.cuda.synchronize()
         outs[grouped] = res
