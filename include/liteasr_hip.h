@@ -665,6 +665,32 @@ int lasr_fbank(const int16_t* pcm, int64_t row_stride, int B, int64_t S, const i
                int max_frames, const float* tab, const int32_t* seg, int F, const float* mean,
                const float* istd, float* out, int Tmax, void* stream);
 
+/* Speed perturbation of task=asr on raw audio (csrc/resample.hip; the reference has none): every
+ * row resampled by its own speed factor p / q (a reduced fraction) with the Hann-windowed sinc of
+ * Kaldi's LinearResample (filter width L = 6, roll-off 0.99), what `speed s` + `rate 16000` do:
+ *   y[m] = sum_n x[n] c sinc(u) cos^2(pi u / 2L),  u = c (n - m p / q),  |u| < L,
+ *   c = 0.99 min(1, q / p),  x[n] = 0 outside [0, n_in),  in polyphase form with width =
+ *   ceil(L / c): output m = j q + i is sum_k x[j p - width + k] tap[i][k], k < 2 width + p;
+ * rounded to nearest-even and saturated to int16, as a 16-bit WAV written in between would.
+ *   pcm [B] rows of S_in int16 samples, in_stride elements apart (2-byte alignment is enough;
+ *     NULL only with S_in = 0);
+ *   plan int32 [B][3] (device, host-drawn): n_in, n_out, ratio index of each row; the kernel
+ *     clamps n_in to [0, S_in] and n_out to [0, S_out];
+ *   ratios int32 [n_ratios][4] (device): p, q, width, offset of the ratio's taps in `taps`;
+ *   taps fp32 [n_taps] (device): per ratio q x (2 width + p) taps, phase-major, as
+ *     liteasr_amd.kernels.resample_tables lays them out (computed in float64 on the host);
+ *     p = q is width 0 and the one tap 1.0: a bit-exact copy;
+ *   out int16 [B] rows of S_out samples, out_stride elements apart, every element written:
+ *     samples m >= n_out are 0 (the zero padding lasr_fbank expects); must not overlap pcm.
+ * A ratio index outside the table, or an entry the kernel cannot hold (p, q outside 1..32,
+ * p > 2 q, width outside 0..13, taps outside n_taps), gives a zero row.  Nothing outside the rows
+ * is read or written whatever the plan holds.  S_in, S_out <= 2^29.  One launch; fp32 fmaf over k
+ * ascending: a sample's bits depend on its phase and its inputs only, not on its place in the
+ * row or batch, the strides or the alignment. */
+int lasr_resample_i16(const int16_t* pcm, int64_t in_stride, int B, int64_t S_in, const int32_t* plan,
+                      const int32_t* ratios, int n_ratios, const float* taps, int64_t n_taps, int16_t* out,
+                      int64_t out_stride, int64_t S_out, void* stream);
+
 /* ------------------------------------------------------------------------
  * SpecAugment (liteasr/utils/transform/spec_augment.py:14-125; applied per utterance in
  * the reference's DataLoader workers, liteasr/dataset/asr_dataset.py:118).  Replaces the

@@ -215,6 +215,7 @@ SIGNATURES = {
                            _p, _p, _p, _p, _i, _p, _p, _i, _p, _p, _p],
     "lasr_pcm_to_float": [_p, _l, _p, _p],
     "lasr_fbank": [_p, _l, _i, _l, _p, _i, _p, _p, _i, _p, _p, _p, _i, _p],
+    "lasr_resample_i16": [_p, _l, _i, _l, _p, _p, _i, _p, _l, _p, _l, _l, _p],
     "lasr_sumsq_nparts": [_l],
     "lasr_sumsq_partial": [_p, _l, _p, _l, _p],
     "lasr_adam_step": [_p, _p, _i, _p, _p, _p, _l, _p, _i, _p, _f, _i, _f, _f, _f, _f, _f, _f,

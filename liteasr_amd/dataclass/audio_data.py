@@ -80,3 +80,25 @@ class WavAudio(Audio):
     @property
     def xlen(self) -> int:
         return self.frames
+
+
+class SpeedWavAudio(WavAudio):
+    """A speed-perturbed copy of a wav.scp utterance (task.frontend.speed_perturb): ``shape`` is
+    the source window's samples as stored, ``ratio`` the speed factor as a reduced fraction
+    (p, q), ``samples`` = ceil(q shape / p) what the device resampler makes of it and ``frames``
+    (``xlen``) the frame count of those.  ``x`` is the source window, unperturbed."""
+
+    __slots__ = ("ratio", "samples")
+
+    def __init__(self, fd, start, shape, tokenids, text, frames: int, ratio: Tuple[int, int], samples: int):
+        super().__init__(fd, start, shape, tokenids, text, frames)
+        self.ratio, self.samples = tuple(ratio), samples
+
+    def __repr__(self):
+        return (f"SpeedWavAudio(fd={self.fd!r}, start={self.start}, shape={self.shape}, ratio={self.ratio}, "
+                f"samples={self.samples}, frames={self.frames}, ylen={self.ylen})")
+
+    def __eq__(self, other):
+        return isinstance(other, SpeedWavAudio) and all(
+            getattr(self, k) == getattr(other, k)
+            for k in Audio.__slots__ + WavAudio.__slots__ + SpeedWavAudio.__slots__)

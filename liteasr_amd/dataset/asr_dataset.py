@@ -21,6 +21,14 @@ feats.scp; utterances below 400 samples (no frame) are dropped with one logged c
 native call (lasr_wav_read_batch) into a zero-padded int16 (B, Smax) tensor and returns it with
 the frame counts; the trainer turns it into features on the GPU (liteasr_amd/utils/frontend.py)
 before the SpecAugment plan, drawn here from the frame counts as for features, is applied.
+
+Speed perturbation (``speed_perturb``, the train split of a raw-audio directory only) is Kaldi's
+static copy: for each factor in the listed order, every utterance in file order, as one
+SpeedWavAudio whose ``xlen`` is the frame count of its ceil(q n / p) resampled samples, so the
+length sort, the batch budgets and the SpecAugment plan see what the model will; a copy left
+without a frame is dropped and counted like a short utterance.  The collator still reads the
+source samples with one native call and appends a ResamplePlan (source and resampled counts and
+the ratio of every row); the resampling itself runs on the device (liteasr_amd/utils/frontend.py).
 """
 
 import logging
@@ -29,11 +37,11 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from ..dataclass.audio_data import Audio, WavAudio
+from ..dataclass.audio_data import Audio, SpeedWavAudio, WavAudio
 from ..dataclass.sheet import AudioSheet, TextSheet
 from ..utils import wavio
 from ..utils.batchify import FrameBatch, SeqBatch
-from ..utils.frontend import num_frames, used_samples
+from ..utils.frontend import ResamplePlan, num_frames, resampled_samples, speed_ratios, used_samples
 from ..utils.kaldiio import read_padded
 from ..utils.transform import PostProcess
 from .liteasr_dataset import LiteasrDataset
@@ -43,7 +51,7 @@ logger = logging.getLogger(__name__)
 
 class AudioFileDataset(LiteasrDataset):
     def __init__(self, split: str, data_dir: str, delimiter: Optional[str], dataset_cfg, postprocess_cfg, vocab,
-                 keep_raw=False, memory_save=False, num_mel_bins: int = 80):
+                 keep_raw=False, memory_save=False, num_mel_bins: int = 80, speed_perturb=None):
         super().__init__()
         if memory_save:
             raise NotImplementedError("memory_save (pickled batch dumps) is not supported")
@@ -57,15 +65,30 @@ class AudioFileDataset(LiteasrDataset):
         texts = TextSheet(data_dir, vocab=vocab, delimiter=delimiter)
         assert len(audios) == len(texts)
         self.wav = audios.scp.endswith("wav.scp")  # raw audio: features come from the device front end
+        self.speed = speed_ratios(speed_perturb) if split == "train" else None  # [(p, q)] or None
+        if self.speed is not None and not self.wav:
+            logger.info("{}: speed_perturb is ignored for a feats.scp directory".format(data_dir))
+            self.speed = None
+        self.speed_table = list(dict.fromkeys(self.speed)) if self.speed is not None else None  # the distinct ratios
         short = 0
-        for (uttid, fd, start, shape), (uttid_t, ids, text) in zip(audios, texts):
-            assert uttid_t == uttid
-            if not self.wav:
-                self.data.append(Audio(fd, start, shape, ids, text if keep_raw else None))
-            elif num_frames(shape) == 0:
-                short += 1
-            else:
-                self.data.append(WavAudio(fd, start, shape, ids, text if keep_raw else None, num_frames(shape)))
+        records = list(zip(audios, texts))
+        for ratio in self.speed if self.speed is not None else [None]:
+            for (uttid, fd, start, shape), (uttid_t, ids, text) in records:
+                assert uttid_t == uttid
+                if not self.wav:
+                    self.data.append(Audio(fd, start, shape, ids, text if keep_raw else None))
+                elif ratio is not None:
+                    p, q = ratio
+                    samples = resampled_samples(shape, p, q)
+                    if num_frames(samples) == 0:
+                        short += 1
+                    else:
+                        self.data.append(SpeedWavAudio(fd, start, shape, ids, text if keep_raw else None,
+                                                       num_frames(samples), (p, q), samples))
+                elif num_frames(shape) == 0:
+                    short += 1
+                else:
+                    self.data.append(WavAudio(fd, start, shape, ids, text if keep_raw else None, num_frames(shape)))
         if short:
             logger.warning("{}: dropped {} utterance(s) shorter than one 25 ms frame".format(data_dir, short))
         self.feat_dim = int(num_mel_bins) if self.wav else self.data[0].x.shape[-1]
@@ -97,7 +120,7 @@ class AudioFileDataset(LiteasrDataset):
         xlens = torch.tensor([s.xlen for s in batch], dtype=torch.long)
         ylens = torch.tensor([s.ylen for s in batch], dtype=torch.long)
         post = self.postprocess if (self.train and self.postprocess is not None and len(self.postprocess)) else None
-        plan = None
+        plan = rplan = None
         if post is not None and post.device_capable:
             # draw the augmentation here (same RNG order as the reference's per-utterance
             # calls); the pixels are produced on the GPU by the trainer (apply_batch)
@@ -107,6 +130,8 @@ class AudioFileDataset(LiteasrDataset):
             if post is not None:
                 raise NotImplementedError("raw-audio batches take device-side postprocessing only (spec_aug)")
             xs = self._collate_pcm(batch)
+            if self.speed is not None:
+                rplan = self._resample_plan(batch)
         elif post is None and all(s.start is None for s in batch):
             tmax = int(xlens.max()) if B else 0
             xs = torch.empty(B, tmax, self.feat_dim, dtype=torch.float32)
@@ -121,9 +146,13 @@ class AudioFileDataset(LiteasrDataset):
         for i, s in enumerate(batch):
             if s.ylen:
                 ys[i, : s.ylen] = torch.tensor(s.tokenids, dtype=torch.long)
-        if plan is not None:
-            return xs, xlens, ys, ylens, plan
-        return xs, xlens, ys, ylens
+        out = (xs, xlens, ys, ylens) if plan is None else (xs, xlens, ys, ylens, plan)
+        return out if rplan is None else out + (rplan,)
+
+    def _resample_plan(self, batch: List[SpeedWavAudio]) -> ResamplePlan:
+        rows = torch.tensor([[s.shape, s.samples, self.speed_table.index(s.ratio)] for s in batch],
+                            dtype=torch.int32).reshape(len(batch), 3)
+        return ResamplePlan(rows, self.speed_table, max((s.samples for s in batch), default=0))
 
     @staticmethod
     def _collate_pcm(batch: List[WavAudio]):
@@ -134,9 +163,10 @@ class AudioFileDataset(LiteasrDataset):
         arr = xs.numpy()
         _, got = wavio.read_batch([s.fd for s in batch], [s.start for s in batch], smax, out=arr)
         for i, s in enumerate(batch):
-            if got[i] < used_samples(s.frames):
+            need = s.shape if isinstance(s, SpeedWavAudio) else used_samples(s.frames)  # resampling reads all
+            if got[i] < need:
                 raise ValueError("{}: {} samples from {} on disk, {} frames need {}".format(
-                    s.fd, int(got[i]), s.start, s.frames, used_samples(s.frames)))
+                    s.fd, int(got[i]), s.start, s.frames, need))
             arr[i, s.shape:] = 0  # a segment's window may run on into the recording
         return xs
 

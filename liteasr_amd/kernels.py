@@ -1252,6 +1252,99 @@ def fbank(pcm, nframes, num_mel_bins=80, cmvn=None, out=None, max_frames=None):
     return out
 
 
+# Speed perturbation (csrc/resample.hip): the Hann-windowed sinc of Kaldi's LinearResample, filter
+# width 6 and roll-off 0.99, per row by a speed factor p / q.
+RESAMPLE_WIDTH, RESAMPLE_ROLLOFF, RESAMPLE_MAX_PQ = 6, 0.99, 32
+
+
+def resample_ratio(speed):
+    """The speed factor as the reduced fraction (p, q) = Fraction(str(speed)); factors outside
+    [0.5, 2] or with p or q above 32 are refused."""
+    from fractions import Fraction
+
+    try:
+        f = Fraction(str(speed))
+    except (ValueError, ZeroDivisionError):
+        raise ValueError(f"speed factor {speed!r} is not a number") from None
+    p, q = f.numerator, f.denominator
+    if not (Fraction(1, 2) <= f <= 2 and p <= RESAMPLE_MAX_PQ and q <= RESAMPLE_MAX_PQ):
+        raise ValueError(f"speed factor {speed!r} is not supported: a factor in [0.5, 2] that reduces to p / q with "
+                         f"p, q <= {RESAMPLE_MAX_PQ} is needed (0.9, 1.0, 1.1)")
+    return p, q
+
+
+def resample_tables(ratios, dtype="float32"):
+    """The kernel's tables for the distinct (p, q) of ``ratios``, computed in float64 on the host:
+    (table int32 [R, 4], taps float32 [n_taps]).  Row r of the table is p, q, width = ceil(L / c)
+    and the offset of the ratio's taps, q x (2 width + p) phase-major: tap[i][k] weighs input
+    j p - width + k in output j q + i,
+      tap[i][k] = c sinc(u) cos^2(pi u / 2L),  u = c (k - width - i p / q),  0 where |u| >= L,
+    c = 0.99 min(1, q / p), L = 6.  p = q is width 0 and the single tap 1: a copy.  ``dtype``
+    float64 gives the taps before their rounding to the kernel's float32."""
+    import numpy as np
+
+    table, blocks, off = [], [], 0
+    for p, q in ratios:
+        p, q = int(p), int(q)
+        if not (1 <= p <= RESAMPLE_MAX_PQ and 1 <= q <= RESAMPLE_MAX_PQ and p <= 2 * q and q <= 2 * p):
+            raise ValueError(f"resample: ratio {p}/{q} is outside [0.5, 2] with p, q <= {RESAMPLE_MAX_PQ}")
+        if np.gcd(p, q) != 1:
+            raise ValueError(f"resample: ratio {p}/{q} is not reduced")
+        if p == q:
+            width, tap = 0, np.ones((1, 1), dtype=np.float64)
+        else:
+            L = float(RESAMPLE_WIDTH)
+            c = RESAMPLE_ROLLOFF * min(1.0, q / p)
+            width = int(np.ceil(L / c))
+            i = np.arange(q, dtype=np.float64)[:, None]
+            k = np.arange(2 * width + p, dtype=np.float64)[None, :]
+            u = c * (k - width - i * p / q)
+            tap = np.where(np.abs(u) < L, c * np.sinc(u) * np.cos(np.pi * u / (2.0 * L)) ** 2, 0.0)
+        table.append((p, q, width, off))
+        blocks.append(tap.reshape(-1))
+        off += tap.size
+    if not table:
+        raise ValueError("resample: no ratio")
+    return np.asarray(table, dtype=np.int32), np.concatenate(blocks).astype(dtype)
+
+
+def resample_i16(pcm, plan, ratios, taps, out=None, max_out=None):
+    """Rows of 16-bit PCM resampled by their own speed factors (lasr_resample_i16): ``pcm`` an
+    int16 device tensor (B, S_in) with contiguous rows (any row stride), ``plan`` int32 (B, 3) on
+    the device (n_in, n_out, ratio index per row), ``ratios`` int32 (R, 4) and ``taps`` fp32 [n]
+    the device copies of ``resample_tables``.  Returns ``out``, int16 (B, S_out) with contiguous
+    rows, every element written: samples m >= n_out[b] are zero.  S_out is out.shape[1], or
+    ``max_out``, the caller's host-side bound on n_out (larger counts are clamped by the
+    kernel); None reads it back from the device, one synchronisation."""
+    if (pcm.dtype != torch.int16 or pcm.dim() != 2 or pcm.device.type != "cuda"
+            or (pcm.shape[1] > 1 and pcm.stride(1) != 1)):
+        raise TypeError("resample_i16: an int16 (B, S) device tensor with contiguous rows is needed")
+    B, S = pcm.shape
+    if (plan.dtype != torch.int32 or plan.device != pcm.device or plan.shape != (B, 3) or not plan.is_contiguous()):
+        raise TypeError("resample_i16: plan must be a contiguous int32 (B, 3) tensor on the device of pcm")
+    if (ratios.dtype != torch.int32 or ratios.device != pcm.device or ratios.dim() != 2 or ratios.shape[1] != 4
+            or ratios.shape[0] < 1 or not ratios.is_contiguous()):
+        raise TypeError("resample_i16: ratios must be a contiguous int32 (R, 4) tensor on the device of pcm")
+    if taps.dtype != torch.float32 or taps.device != pcm.device or taps.dim() != 1 or not taps.is_contiguous():
+        raise TypeError("resample_i16: taps must be a contiguous fp32 vector on the device of pcm")
+    if out is None:
+        if max_out is None:
+            max_out = int(plan[:, 1].max()) if B else 0
+        if int(max_out) < 0:
+            raise ValueError(f"resample_i16: max_out = {max_out} is negative")
+        out = torch.empty(B, int(max_out), dtype=torch.int16, device=pcm.device)
+    elif (out.dtype != torch.int16 or out.device != pcm.device or out.dim() != 2 or out.shape[0] != B
+          or (out.shape[1] > 1 and out.stride(1) != 1) or (B > 1 and out.shape[1] and out.stride(0) < out.shape[1])):
+        raise TypeError("resample_i16: out must be an int16 (B, S_out) tensor with contiguous rows on the device of "
+                        "pcm")
+    elif max_out is not None and int(max_out) > out.shape[1]:
+        raise ValueError(f"resample_i16: out holds {out.shape[1]} samples per row, max_out is {max_out}")
+    N.call("lasr_resample_i16", ptr(pcm), pcm.stride(0) if B > 1 else S, B, S, ptr(plan), ptr(ratios),
+           ratios.shape[0], ptr(taps), taps.numel(), ptr(out), out.stride(0) if B > 1 else out.shape[1],
+           out.shape[1], stream())
+    return out
+
+
 def scale_add(a, b, sa, sb, out):
     N.call("lasr_scale_add", ptr(a), dt(a), ptr(b), dt(b) if b is not None else 0, sa, sb,
            ptr(out), dt(out), out.numel(), stream())

@@ -4,7 +4,9 @@ Data directories with feats.scp are read as the reference reads them.  A directo
 and no feats.scp is raw audio: the task's front end (``task.frontend``: Kaldi fbank with
 ``num_mel_bins`` filters and optional global CMVN statistics, liteasr_amd/utils/frontend.py)
 computes the features on the device, in the trainer and in ``inference``.  Every other Kaldi
-fbank option is fixed at the value documented there; ``dither`` other than 0 is refused."""
+fbank option is fixed at the value documented there; ``dither`` other than 0 is refused.
+``task.frontend.speed_perturb`` (a list of speed factors) applies to the train split of a raw-audio
+directory only: valid and test splits, ``inference`` and feats.scp directories ignore it."""
 
 import inspect
 import logging
@@ -18,7 +20,7 @@ import torch
 from ..config import MISSING, LiteasrDataclass
 from ..dataclass.vocab import Vocab
 from ..dataset import AudioFileDataset
-from ..utils.frontend import Fbank, num_frames
+from ..utils.frontend import Fbank, num_frames, speed_ratios
 from . import LiteasrTask, register_task
 
 logger = logging.getLogger(__name__)
@@ -31,6 +33,9 @@ class FrontendConfig(LiteasrDataclass):
     num_mel_bins: int = field(default=80)
     cmvn: Optional[str] = field(default=None)  # Kaldi global CMVN statistics, 2 x (num_mel_bins + 1)
     dither: float = field(default=0.0)  # only 0 is supported
+    # speed factors of the train split, e.g. [0.9, 1.0, 1.1]: one copy of every utterance per factor,
+    # resampled on the device in front of the fbank kernel (None: off)
+    speed_perturb: Optional[List[float]] = field(default=None)
 
 
 @dataclass
@@ -44,11 +49,15 @@ class ASRConfig(LiteasrDataclass):
     frontend: FrontendConfig = field(default_factory=FrontendConfig)
 
 
-def _frontend_of(cfg) -> Fbank:
+def _frontend_get(cfg):
     fe = cfg.get("frontend") if isinstance(cfg, dict) else getattr(cfg, "frontend", None)
     if fe is None:
-        return Fbank()
-    get = fe.get if isinstance(fe, dict) else lambda k, d=None: getattr(fe, k, d)
+        return lambda k, d=None: d
+    return fe.get if isinstance(fe, dict) else lambda k, d=None: getattr(fe, k, d)
+
+
+def _frontend_of(cfg) -> Fbank:
+    get = _frontend_get(cfg)
     return Fbank(num_mel_bins=get("num_mel_bins", 80), cmvn=get("cmvn", None), dither=float(get("dither", 0.0) or 0.0))
 
 
@@ -62,6 +71,9 @@ class ASRTask(LiteasrTask):
         self.vocab_size = len(self.vocab)
         self.feat_dim = 0
         self.frontend = _frontend_of(cfg)
+        sp = _frontend_get(cfg)("speed_perturb", None)
+        self.speed_perturb = [float(s) for s in sp] if sp else None
+        speed_ratios(self.speed_perturb)  # a factor the resampler does not take is refused here
 
     def load_dataset(self, split: str, data_dir: Union[str, list], dataset_cfg=None, postprocess_cfg=None,
                      memory_save: bool = False):
@@ -71,7 +83,8 @@ class ASRTask(LiteasrTask):
             logger.info("loading {} data from {}".format(split, d))
             return AudioFileDataset(split=split, data_dir=d, delimiter=self.cfg.delimiter, dataset_cfg=dataset_cfg,
                                     postprocess_cfg=postprocess_cfg, vocab=self.vocab, keep_raw=split == "test",
-                                    memory_save=memory_save, num_mel_bins=self.frontend.num_mel_bins)
+                                    memory_save=memory_save, num_mel_bins=self.frontend.num_mel_bins,
+                                    speed_perturb=self.speed_perturb if split == "train" else None)
 
         if isinstance(data_dir, str):
             self.datasets[split] = one(data_dir)

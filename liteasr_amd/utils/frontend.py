@@ -12,6 +12,12 @@ CMVN statistics are the configuration.
 CMVN statistics are Kaldi's global matrix, ``2 x (F + 1)`` as ``compute-cmvn-stats`` writes it
 (row 0: sums and the frame count, row 1: sums of squares and 0), binary or text:
 ``mean = s / c`` and ``istd = 1 / sqrt(max(ss / c - mean^2, 1e-20))``.
+
+Speed perturbation (``frontend.speed_perturb``, e.g. [0.9, 1.0, 1.1]; the train split only) runs in
+front of it, on the device too: the collator still delivers the source int16 batch, with a
+ResamplePlan, and ``lasr_resample_i16`` (csrc/resample.hip) makes the int16 batch the fbank kernel
+reads: Kaldi's LinearResample (Hann-windowed sinc, filter width 6, roll-off 0.99), rounded and
+saturated to 16 bits like the WAV file an offline ``speed`` + ``rate`` pipeline writes.
 """
 
 import numpy as np
@@ -75,10 +81,65 @@ def cmvn_from_stats(stats):
     return mean, 1.0 / np.sqrt(np.maximum(var, 1e-20))
 
 
+def speed_ratios(speed_perturb):
+    """``frontend.speed_perturb`` as the list of reduced fractions (p, q), in the listed order;
+    None or an empty list is None.  A factor outside [0.5, 2] or with p, q above 32 is refused."""
+    if not speed_perturb:
+        return None
+    from ..kernels import resample_ratio
+
+    return [resample_ratio(s) for s in speed_perturb]
+
+
+def resampled_samples(nsamples: int, p: int, q: int) -> int:
+    """Samples of an utterance of ``nsamples`` at speed p / q: ceil(q n / p)."""
+    return -((-q * int(nsamples)) // p)
+
+
+class ResamplePlan(object):
+    """What the collator of a speed-perturbed dataset adds to its batch, as the last element:
+    ``rows`` int32 (B, 3) on the host, per row its source samples, its resampled samples and the
+    index of its ratio in ``ratios``, the dataset's distinct (p, q); ``max_out`` the largest
+    resampled count.  Trainer._features takes it off the batch again."""
+
+    __slots__ = ("rows", "ratios", "max_out")
+
+    def __init__(self, rows, ratios, max_out: int):
+        self.rows, self.ratios, self.max_out = rows, tuple(tuple(r) for r in ratios), int(max_out)
+
+
+class SpeedPerturb(object):
+    """int16 (B, S) PCM on the device + a ResamplePlan -> the resampled int16 (B, max_out) batch,
+    zero past every row's own samples (``lasr_resample_i16``).  The ratio and tap tables are made
+    once per set of ratios and device."""
+
+    def __init__(self):
+        self._dev = {}
+
+    def tables_on(self, ratios, device):
+        import torch
+
+        from .. import kernels as K
+
+        key = (tuple(tuple(r) for r in ratios), torch.device(device))
+        if key not in self._dev:
+            self._dev[key] = tuple(torch.from_numpy(v).to(key[1]) for v in K.resample_tables(key[0]))
+        return self._dev[key]
+
+    def __call__(self, pcm, plan: ResamplePlan, out=None):
+        from .. import kernels as K
+
+        table, taps = self.tables_on(plan.ratios, pcm.device)
+        return K.resample_i16(pcm, plan.rows.to(pcm.device), table, taps, out=out, max_out=plan.max_out)
+
+
 class Fbank(object):
-    """int16 (B, S) PCM on the device + frame counts -> fp32 (B, T, F) features, zero-padded."""
+    """int16 (B, S) PCM on the device + frame counts -> fp32 (B, T, F) features, zero-padded.
+    ``speed``: the speed perturbation that runs in front of it on training batches that carry a
+    ResamplePlan."""
 
     def __init__(self, num_mel_bins: int = 80, cmvn: str = None, dither: float = 0.0):
+        self.speed = SpeedPerturb()
         if dither != 0:
             raise NotImplementedError("frontend.dither: dithering (a device RNG in the front end) is not supported")
         self.num_mel_bins = int(num_mel_bins)
