@@ -9,7 +9,7 @@ from dataclasses import dataclass, field
 from typing import Optional
 
 from ..config import MISSING, LiteasrDataclass
-from ..nets.functional import HybridLossFn
+from ..nets.losses import HybridLossFn
 from . import LiteasrLoss, register_criterion
 
 

@@ -5,7 +5,7 @@ from dataclasses import dataclass, field
 from typing import Optional
 
 from ..config import MISSING, LiteasrDataclass
-from ..nets.functional import ParaformerLossFn
+from ..nets.losses import ParaformerLossFn
 from . import LiteasrLoss, register_criterion
 
 

@@ -10,7 +10,7 @@ from typing import Optional
 import torch
 
 from ..config import LiteasrDataclass
-from ..nets.functional import RNNTLossFn
+from ..nets.losses import RNNTLossFn
 from . import LiteasrLoss, register_criterion
 
 

@@ -2,7 +2,7 @@
 beam search (liteasr/models/transducer.py:137-206; device-resident, csrc/rnnt_search.hip).
 
 Device side: the encoder / decoder run through the same HIP kernels as training
-(nets/functional.py: encoder_out, ctc_logits, decoder_logits); per-frame log_softmax +
+(nets/decode.py: encoder_out, ctc_logits, decoder_logits); per-frame log_softmax +
 top-k and the rescoring gathers are one HIP kernel (lasr_logsoftmax_topk).  Host side:
 the CTC prefix beam search is native C++ (libliteasr_decode.so, csrc/decode/), fed
 with the [T', beam] candidates; the attention beam's (beam x beam) bookkeeping is a few
@@ -20,7 +20,7 @@ import torch
 
 from . import kernels as K
 from .graph_step import collect_before_capture
-from .nets import functional as FN
+from .nets import decode as DN
 
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libliteasr_decode.so")
 _LIB = None
@@ -117,13 +117,13 @@ def _encode_eager(model, x, fp32=False):
     ys = torch.full((B, 1), -1, dtype=torch.int64, device=x.device)
     ylens = torch.zeros(B, dtype=torch.int64, device=x.device)
     xe, prep, _ = model._run_encoder(x, xlens, ys, ylens)
-    return FN.encoder_out(xe, model, torch.float32 if fp32 else model.compute_dtype), prep.T
+    return DN.encoder_out(xe, model, torch.float32 if fp32 else model.compute_dtype), prep.T
 
 
 def ctc_prefix_beam_search_nbest(model, x, beam=10):
     """u2.py:218-263: (n-best [(tokens, score)], h [T', d], T')."""
     h, T = encode(model, x)
-    logits = FN.ctc_logits(h, model)
+    logits = DN.ctc_logits(h, model)
     vals, idx, _ = K.logsoftmax_topk(logits, min(beam, logits.shape[1]))
     hyps = prefix_beam_search(vals.cpu().numpy(), idx.cpu().numpy(), beam, model.blank)
     return hyps, h, T
@@ -144,7 +144,7 @@ def rescore(model, hyps, h, T, ctc_weight=0.5):
     Tx = 4 * T + 3  # any Tx with ((Tx-1)//2-1)//2 == T; all frames valid
     prep = model._prep_targets(ys.to(dev), ylens.to(dev), n, Tx)
     mem = h.view(1, T, -1).expand(n, T, h.shape[1]).reshape(n * T, h.shape[1])
-    h_attn = FN.decoder_logits(model, mem, prep.ys_in, prep.dec_mask, _mem_mask(n, T, dev), n, L1, T)
+    h_attn = DN.decoder_logits(model, mem, prep.ys_in, prep.dec_mask, _mem_mask(n, T, dev), n, L1, T)
     gidx = torch.full((n, L1), -1, dtype=torch.int32)
     for i, (t, _) in enumerate(hyps):
         gidx[i, :len(t)] = torch.tensor(t, dtype=torch.int32)
@@ -172,7 +172,7 @@ def pick_best(hyps, g, ctc_weight=0.5):
 def attention_beam_search(model, x, beam=10, trace=None):
     """u2.py:163-216: left-to-right attention beam search (memory h repeated, no memory
     mask), max T' steps, the decoder advanced one position per step through its key/value
-    cache (FN.DecoderStepCache: the reference's forward_one_step cache semantics, incl. its
+    cache (DN.DecoderStepCache: the reference's forward_one_step cache semantics, incl. its
     never-reordered cache of layers >= 1), per-step log_softmax + topk(beam) on the device,
     the (beam x beam) score bookkeeping in float32 on the host.  trace (a list): per step
     (hyps fed to the step [beam, i], log-prob top-k values [beam, beam]) for tests."""
@@ -183,7 +183,7 @@ def attention_beam_search(model, x, beam=10, trace=None):
     hyps = np.full((beam, 1), sos, dtype=np.int64)
     scores = init.reshape(beam, 1).copy()
     end = np.zeros(beam, dtype=bool)
-    dec = FN.DecoderStepCache(model, h, beam, T, T + 1)
+    dec = DN.DecoderStepCache(model, h, beam, T, T + 1)
     sel_d = None
     for i in range(1, T + 1):
         if end.sum() == beam:
@@ -221,7 +221,7 @@ def attention_rescore_host(model, x, ctc_weight=0.5, encoder_graph=True):
         hyps, h, T = ctc_prefix_beam_search_nbest(model, x, beam=10)
     else:
         h, T = encode(model, x, graph=False)
-        logits = FN.ctc_logits(h, model)
+        logits = DN.ctc_logits(h, model)
         vals, idx, _ = K.logsoftmax_topk(logits, min(10, logits.shape[1]))
         hyps = prefix_beam_search(vals.cpu().numpy(), idx.cpu().numpy(), 10, model.blank)
     return tuple(hyps[rescore(model, hyps, h, T, ctc_weight=ctc_weight)][0])
@@ -267,14 +267,14 @@ class _Rescore:
         decoder inputs, the decoder at (10, L1cap, Tcap) under the memory mask, the gather, the
         pick: one stream, in this order."""
         Tcap, Lcap, L1 = self.Tcap, self.Lcap, self.L1
-        logits = FN.ctc_logits(self.mem, model)
+        logits = DN.ctc_logits(self.mem, model)
         vals, idx, _ = K.logsoftmax_topk(logits, self.k)
         K.rescore_search(self.arena, Tcap, Lcap, vals, idx, self.tp, model.blank, _BEAM)
         K.rescore_prep(self.arena, Tcap, Lcap, model.sos, model.eos, self.ys_in, self.dec_mask, self.gidx,
                        self.mem_mask)
         d = self.mem.shape[1]
         mem = self.mem.view(1, Tcap, d).expand(_BEAM, Tcap, d).reshape(_BEAM * Tcap, d)
-        h_attn = FN.decoder_logits(model, mem, self.ys_in, self.dec_mask, self.mem_mask, _BEAM, L1, Tcap)
+        h_attn = DN.decoder_logits(model, mem, self.ys_in, self.dec_mask, self.mem_mask, _BEAM, L1, Tcap)
         _, _, g = K.logsoftmax_topk(h_attn, 0, gather_idx=self.gidx)
         K.rescore_pick(self.arena, Tcap, Lcap, g, _CTC_WEIGHT)
         return vals, idx, g

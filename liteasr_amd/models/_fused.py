@@ -225,9 +225,8 @@ class FusedEncoderModel(LiteasrModel):
             B=B, T=T, L1=L1, H=enc.n_head, adt=self.compute_dtype, training=tr,
             p_drop=er.drop, p_ff=er.ff, p_att=er.att, p_pos=er.pos if tr else 0.0,
             p_ctc=ctc.dropout_rate if ctc is not None else 0.0,  # always on (liteasr/nets/ctc.py:29)
-            p_dec=dr.drop, p_dec_ff=dr.ff, p_dec_att=dr.self_att, p_dec_src_att=dr.src_att,
-            p_dec_pos=getattr(dr, "pos", 0.0), ys_in=prep.ys_in, dec_mask=prep.dec_mask, mask_k=prep.enc_mask,
-            seed=self._seed_base, links=None)
+            p_dec_pos=getattr(dr, "pos", 0.0),  # (the decoder's other rates: functional.decoder_rates)
+            ys_in=prep.ys_in, dec_mask=prep.dec_mask, mask_k=prep.enc_mask, seed=self._seed_base, links=None)
         if prep.chunk_mask is not None:
             env.mask, env.msb, env.msq = prep.chunk_mask, prep.chunk_mask.stride(0), prep.chunk_mask.stride(1)
         else:

@@ -4,7 +4,7 @@ Same config schema, registry name ("Paraformer"), state_dict keys and call conve
 the reference: ``model(xs, xlens, ys, ylens) -> (hs_attn (B, L, V), sum_alpha (B,))``,
 with ``ParaformerLoss`` (criterions/paraformer_loss.py) on top.  The encoder is U2's fused
 Conformer stack (models/_fused.py); everything after it is one fused autograd node
-(nets/functional.py ParaformerHeadsFn): CIF predictor with the integrate-and-fire scan in
+(nets/paraformer.py ParaformerHeadsFn): CIF predictor with the integrate-and-fire scan in
 csrc/cif.hip, the parallel decoder on the decoder-layer kernels, the glancing sampler.
 
 The glancing sampler draws with Python's ``random`` module exactly like the reference
@@ -26,8 +26,8 @@ import torch.nn as nn
 from torch import Tensor
 
 from ..config import II, MISSING, LiteasrDataclass
-from ..nets import functional as FN
 from ..nets.modules import ParallelDecoder, PositionalEncoding, Predictor, TransformerEncoder
+from ..nets.paraformer import ParaformerHeadsFn, paraformer_decode
 from . import register_model
 from ._fused import FusedEncoderModel, _require_hip
 
@@ -116,7 +116,7 @@ class Paraformer(FusedEncoderModel):
         env.pred_len, env.ylen = prep.pred_len, prep.ylen
         ylens_host = ylens.detach().cpu().long()
         ys_d = ys.to(device=xs.device, dtype=torch.int64)
-        hs_attn, sum_alpha = FN.ParaformerHeadsFn.apply(x, self.predictor.conv.weight, self, env, ys_d,
+        hs_attn, sum_alpha = ParaformerHeadsFn.apply(x, self.predictor.conv.weight, self, env, ys_d,
                                                         ylens_host, self.rng)
         self.last_count = int(ylens_host.sum())
         return hs_attn.view(prep.B, ys.shape[1], -1), sum_alpha
@@ -136,7 +136,7 @@ class Paraformer(FusedEncoderModel):
         h, _ = self.encode(xs, xl)
         prep = self.last_prep
         B, T = prep.B, prep.T
-        cif, ulens, ids, logits = FN.paraformer_decode(self, h.reshape(B * T, -1), prep.pred_len, prep.enc_mask, B, T)
+        cif, ulens, ids, logits = paraformer_decode(self, h.reshape(B * T, -1), prep.pred_len, prep.enc_mask, B, T)
         self.last_decode = SimpleNamespace(cif=cif, ulens=ulens, logits=logits, h=h)
         return [[] if ids is None else ids[b, :u].tolist() for b, u in enumerate(ulens)]
 
@@ -156,7 +156,7 @@ class Paraformer(FusedEncoderModel):
         h, _ = decoding.encode(self, x, fp32=True)
         plen = torch.full((1,), T, dtype=torch.int32, device=x.device)
         mask = torch.zeros(1, T, dtype=torch.uint8, device=x.device)
-        cif, ulens, ids, logits = FN.paraformer_decode(self, h, plen, mask, 1, T)
+        cif, ulens, ids, logits = paraformer_decode(self, h, plen, mask, 1, T)
         self.last_decode = SimpleNamespace(cif=cif, ulens=ulens, logits=logits, h=h)
         return [] if ids is None else ids[0, :ulens[0]].tolist()
 

@@ -6,7 +6,7 @@ logits; the RNN-T criterion, criterions/rnnt.py, applies the log-softmax), get_p
 get_target / get_target_len.  The encoder is U2's fused Conformer stack (models/_fused.py);
 everything after it -- encoder after_norm, lin_enc, the LSTM prediction network
 (nets/rnn_decoder.py), lin_dec, the tanh joint and lin_jnt -- is one fused autograd node
-(nets/functional.py TransducerHeadsFn) on csrc/rnnt.hip and the GEMM kernels.
+(nets/transducer.py TransducerHeadsFn) on csrc/rnnt.hip and the GEMM kernels.
 
 Initialisation follows the reference's _init_module (transducer.py:223-231: LeCun normal for
 the prediction network and the three joint projections, N(0, 1) embedding, forget-gate
@@ -26,8 +26,8 @@ import torch.nn as nn
 from torch import Tensor
 
 from ..config import II, MISSING, LiteasrDataclass
-from ..nets import functional as FN
 from ..nets.modules import Joint, RNNDecoder, TransformerEncoder
+from ..nets.transducer import TransducerHeadsFn
 from ..utils.cfg import enum_value
 from . import register_model
 from ._fused import FusedEncoderModel
@@ -139,7 +139,7 @@ class Transducer(FusedEncoderModel):
         ys_in = torch.cat([torch.zeros(B, 1, dtype=torch.int64, device=xs.device),
                            ys_d.masked_fill(ys_d == self.ignore, self.blank)], 1)
         ids = ys_in.t().contiguous().view(-1).to(torch.int32)
-        h = FN.TransducerHeadsFn.apply(x, self.lin_jnt.weight, self, env, ids, U1)
+        h = TransducerHeadsFn.apply(x, self.lin_jnt.weight, self, env, ids, U1)
         return h.view(B, T, U1, self.vocab_size)
 
     def inference(self, x):

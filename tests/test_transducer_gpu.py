@@ -1,5 +1,5 @@
-"""Transducer head + RNN-T loss on the GPU (csrc/rnnt.hip, nets/functional.py
-TransducerHeadsFn / RNNTLossFn) against the oracles:
+"""Transducer head + RNN-T loss on the GPU (csrc/rnnt.hip, nets/transducer.py
+TransducerHeadsFn, nets/losses.py RNNTLossFn) against the oracles:
 
 * the RNN-T kernels vs oracle/rnnt_ref.py (float64 restatement of the published algorithm,
   pinned by path enumeration and finite differences in tests/test_rnnt.py; the reference's
@@ -45,7 +45,7 @@ def _lattice_case(B, T, U, V, dtype, seed):
                                            (4, 249, 40, 4233, torch.bfloat16), (2, 60, 150, 97, torch.float32)])
 def test_rnnt_kernels_match_restatement(B, T, U, V, dtype):
     from liteasr_amd import kernels as K
-    from liteasr_amd.nets.functional import RNNTLossFn
+    from liteasr_amd.nets.losses import RNNTLossFn
 
     z, ys, xl, yl = _lattice_case(B, T, U, V, dtype, seed=T + U)
     buf = K.padded_rows(B * T * (U + 1), V, dtype, "cuda").view(B, T, U + 1, V)

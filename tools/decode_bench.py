@@ -31,7 +31,7 @@ def main():
     from liteasr_amd import decoding as D
     from liteasr_amd import kernels as K
     from liteasr_amd.models.u2 import U2, U2Config
-    from liteasr_amd.nets import functional as FN
+    from liteasr_amd.nets import decode as DN
     from liteasr_amd.utils.cfg import resolve_self
     from oracle import decode_ref as R
 
@@ -58,7 +58,7 @@ def main():
         out["attention_rescore_ms"] = timed(lambda: model.attention_rescore(x))
         out["encoder_ms"] = timed(lambda: D.encode(model, x))
         h, T = D.encode(model, x)
-        logits = FN.ctc_logits(h, model)
+        logits = DN.ctc_logits(h, model)
         V = logits.shape[1]
         s = torch.cuda.current_stream()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
