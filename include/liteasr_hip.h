@@ -157,6 +157,14 @@ int lasr_gemm_dw_group_order(int longest_first);
 /* Planner switch for narrow outputs (N <= 64): 1 (default) = 64 x 64 tiles, 0 = the
  * fill-the-chip tile order of wider outputs; the results are the same bits. */
 int lasr_gemm_narrow_tiles(int on);
+/* Routing of the long-K, N = d family (bf16, A K-contiguous, K % 64 == 0, residual + dropout fp32
+ * or plain bf16 epilogue) to the phased 128 x 64 kernel, one workgroup per CU: 1 (default) = when
+ * K >= 1024 and the tiles number 3/4 to 1 x the CU count, 0 = never, 2 = whatever the sizes.  The
+ * results are the same bits; the routing is not part of lasr_gemm_plan. */
+int lasr_gemm_phased(int mode);
+/* Number of lasr_gemm calls this process has launched on that kernel (tools and tests read it
+ * around a call). */
+long long lasr_gemm_phased_launches(void);
 
 /* Batched partial reductions (one launch for a backward node's deferred parameter
  * gradients): out[n] (+)= sum_p part[p*N + n], n < split -> out0[n], else out1[n-split].

@@ -139,6 +139,8 @@ SIGNATURES = {
     "lasr_gemm_dw_group": [C.POINTER(GemmArgs), _i, _p],
     "lasr_gemm_dw_group_order": [_i],
     "lasr_gemm_narrow_tiles": [_i],
+    "lasr_gemm_phased": [_i],
+    "lasr_gemm_phased_launches": [],
     "lasr_relattn_fwd": [_p, _p, _l, _p, _p, _l, _p, _l, _i, _i, _i, _i, _p, _l, _l, _f, _p, _p, _l, _p],
     "lasr_relattn_fwd_qb": [_p, _l, _p, _p, _p, _p, _l, _p, _p, _l, _p, _l, _i, _i, _i, _i, _p, _l, _l, _f, _p, _p,
                             _l, _p],
@@ -252,7 +254,7 @@ SIGNATURES = {
 _RESTYPES = {"lasr_last_error": C.c_char_p, "lasr_spec_augment_ws_bytes": C.c_int64,
              "lasr_rnnt_search_workspace": C.c_int64, "lasr_rescore_workspace": C.c_int64,
              "lasr_conv2_dx_w1_workspace": C.c_int64, "lasr_attn_split_work": C.c_int64,
-             "lasr_dropout_scale": C.c_float}
+             "lasr_dropout_scale": C.c_float, "lasr_gemm_phased_launches": C.c_int64}
 
 
 class NativeError(RuntimeError):

@@ -15,6 +15,7 @@
 // attention.py:35-37,58,69,145,149, subsampling.py:34,47, conformer_convolution.py:48,55,
 // ctc.py:29, transformer_decoder.py:91 (and their autograd backward GEMMs).
 #include "gemm_kernel.h"
+#include "gemm_phase.h"
 #include <algorithm>
 
 // ================================ host launcher ==================================
@@ -287,9 +288,14 @@ int gemm_run(const lasr_gemm_args* a, void* stream, GemmRowPost* post) {
     p.rowsum = a->rowsum;
     if (split > 1) p.rs_ws = p.ws + (int64_t)split * batch * a->M * a->N;
   }
-  if (a->c_dtype == LASR_F32) dispatch<float>(p, akc, bkc, bf, BM, BN, ks, nw, glds, grid, st);
+  // the long-K, N = d family on one 128 x 64 workgroup per CU (gemm_phase.hip: same bits);
+  // decided here, so the plan lasr_gemm_plan reports stays the planner's
+  const bool phased = gemm_phased_launch(a, p, glds, st);
+  if (phased) {
+  } else if (a->c_dtype == LASR_F32) dispatch<float>(p, akc, bkc, bf, BM, BN, ks, nw, glds, grid, st);
   else dispatch<bf16_t>(p, akc, bkc, bf, BM, BN, ks, nw, glds, grid, st);
   int rc = lasr_check_launch("lasr_gemm");
+  if (phased && !rc) gemm_phased_count();
   if (!rc && split > 1 && a->split_k >= 0 && post) {  // a row post-op may take over the reduction
     const int r = post->launch(p, post->ctx, st);
     if (r < 0) return r;
