@@ -847,6 +847,32 @@ int lasr_rescore_prep(const void* arena, int64_t arena_bytes, int Tcap, int Lcap
 int lasr_rescore_pick(void* arena, int64_t arena_bytes, int Tcap, int Lcap, const float* gathered,
                       double ctc_weight, void* stream);
 
+/* The same three entries for B utterances at once (1 <= B <= 4096); the single-utterance entries
+ * above are their B = 1 launches.  The batch arena is B single-utterance arenas laid end to end:
+ * utterance b owns bytes [b S, (b + 1) S), S = lasr_rescore_workspace(Tcap, Lcap), and its result
+ * block reads exactly as above.  The utterances share nothing.
+ *
+ * lasr_rescore_workspace_batch: B * S (0 for a B outside the range).
+ * lasr_rescore_search_batch (u2.py:218-263 per utterance): B workgroups after ONE launch that
+ *   empties all B prefix tables; workgroup b searches topk_val / topk_idx [b Tcap k, (b + 1) Tcap k)
+ *   over T'_b = Tp_dev[b] frames.  A row with T'_b = 0 runs no frame and touches no table slot:
+ *   n = 1, the empty prefix with score 0.
+ * lasr_rescore_prep_batch (u2.py:268-298 per utterance): ys_in [B][10][L1cap], dec_mask
+ *   [B][10][L1cap][dec_ld], gather_idx [B 10 L1cap], mem_mask [B][10][Tcap].  The memory mask of
+ *   utterance b is 1 at frames >= mem_len[b] (a device word per utterance: the encoder's own
+ *   subsampled padding mask, transformer_encoder.py:107-127, which may be longer than T'_b), not
+ *   at frames >= T'_b.
+ * lasr_rescore_pick_batch (u2.py:300-315 per utterance): gathered [B][10][L1cap], one workgroup
+ *   per utterance. */
+int64_t lasr_rescore_workspace_batch(int B, int Tcap, int Lcap);
+int lasr_rescore_search_batch(void* arena, int64_t arena_bytes, int B, int Tcap, int Lcap, int k, int blank, int beam,
+                              const float* topk_val, const int32_t* topk_idx, const int32_t* Tp_dev, void* stream);
+int lasr_rescore_prep_batch(const void* arena, int64_t arena_bytes, int B, int Tcap, int Lcap, int sos, int eos,
+                            int32_t* ys_in, uint8_t* dec_mask, int dec_ld, int32_t* gather_idx, uint8_t* mem_mask,
+                            const int32_t* mem_len, void* stream);
+int lasr_rescore_pick_batch(void* arena, int64_t arena_bytes, int B, int Tcap, int Lcap, const float* gathered,
+                            double ctc_weight, void* stream);
+
 /* ---- wav2vec 2.0 pretraining (csrc/w2v.hip) -----------------------------------------
  * Activations are channels-last: [B][T][C].  `dtype` arguments are LASR_F32 / LASR_BF16.
  * Every parameter-gradient output ACCUMULATES (+=) in a fixed summation order; no entry

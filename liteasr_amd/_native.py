@@ -233,6 +233,10 @@ SIGNATURES = {
     "lasr_rescore_search": [_p, _l, _i, _i, _i, _i, _i, _p, _p, _p, _p],
     "lasr_rescore_prep": [_p, _l, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p],
     "lasr_rescore_pick": [_p, _l, _i, _i, _p, C.c_double, _p],
+    "lasr_rescore_workspace_batch": [_i, _i, _i],
+    "lasr_rescore_search_batch": [_p, _l, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p],
+    "lasr_rescore_prep_batch": [_p, _l, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p],
+    "lasr_rescore_pick_batch": [_p, _l, _i, _i, _i, _p, C.c_double, _p],
     "lasr_w2v_conv0_fwd": [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p],
     "lasr_w2v_conv0_dw_parts": [_i, _i],
     "lasr_w2v_conv0_dw": [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _l, _p],
@@ -253,6 +257,7 @@ SIGNATURES = {
 }
 _RESTYPES = {"lasr_last_error": C.c_char_p, "lasr_spec_augment_ws_bytes": C.c_int64,
              "lasr_rnnt_search_workspace": C.c_int64, "lasr_rescore_workspace": C.c_int64,
+             "lasr_rescore_workspace_batch": C.c_int64,
              "lasr_conv2_dx_w1_workspace": C.c_int64, "lasr_attn_split_work": C.c_int64,
              "lasr_dropout_scale": C.c_float, "lasr_gemm_phased_launches": C.c_int64}
 

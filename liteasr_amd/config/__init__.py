@@ -90,6 +90,8 @@ class InferenceConfig(LiteasrDataclass):
     avg_num: int = field(default=1)
     avg_policy: Optional[str] = field(default=II("run_cfg.dir") + "/train.log")
     thread_num: int = field(default=32)
+    # liteasr_amd extension: utterances decoded per model.inference_batch call (1: one at a time)
+    batch_size: int = field(default=1)
 
 
 @dataclass

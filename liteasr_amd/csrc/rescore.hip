@@ -36,6 +36,13 @@
 // compare-and-swap on an empty slot is the whole insert.  Table traffic goes to L2 (agent-scope
 // loads, atomics); everything else of a frame lives in LDS.
 //
+// Batch.  Every kernel takes B utterances: the batch arena is B single-utterance arenas laid end
+// to end (stride = lasr_rescore_workspace(Tcap, Lcap) bytes), workgroup / grid row b works on
+// arena b, on candidates [b Tcap k, ...), on Tp_dev[b], and on row b of the decoder inputs.  The
+// utterances share nothing, so B workgroups of the serial search cost what one costs; a row with
+// T' = 0 runs no frame, touches no table slot and reports n = 1, the empty prefix.  The
+// single-utterance entries are the B = 1 launches.
+//
 // Built without contraction (Makefile: -ffp-contract=off for this file; the pragma below
 // says the same) and without fast-math: + and the comparisons are the IEEE operations of the
 // reference's Python floats.
@@ -118,8 +125,10 @@ LASR_DEV int child_slot(uint64_t* table, int64_t cap, int parent, int token) {
   return -1;
 }
 
-// every slot of the prefix table empty: one 16-B store (two keys) per thread
-__global__ __launch_bounds__(256) void rescore_clear_kernel(uint4* __restrict__ table) {
+// every slot of the prefix tables empty: one 16-B store (two keys) per thread; grid row y = the
+// utterance, its table `stride` bytes after the previous one
+__global__ __launch_bounds__(256) void rescore_clear_kernel(char* __restrict__ table0, int64_t stride) {
+  uint4* table = (uint4*)(table0 + (int64_t)blockIdx.y * stride);
   table[(int64_t)blockIdx.x * 256 + threadIdx.x] = make_uint4(~0u, ~0u, ~0u, ~0u);
 }
 
@@ -129,11 +138,15 @@ struct RankKey {
   int pad;
 };
 
-__global__ __launch_bounds__(kThreads) void rescore_search_kernel(int32_t* __restrict__ arena, int Tcap, int Lcap, int k,
-                                                                  int blank, const float* __restrict__ topv,
-                                                                  const int32_t* __restrict__ topi,
+__global__ __launch_bounds__(kThreads) void rescore_search_kernel(int32_t* __restrict__ arena0, int Tcap, int Lcap, int k,
+                                                                  int blank, const float* __restrict__ topv0,
+                                                                  const int32_t* __restrict__ topi0,
                                                                   const int32_t* __restrict__ Tp_dev) {
   const Layout L = make_layout(Tcap, Lcap);
+  const int b = blockIdx.x;  // the utterance: its arena, its candidates, its T'
+  int32_t* arena = (int32_t*)((char*)arena0 + (int64_t)b * L.total);
+  const float* topv = topv0 + (int64_t)b * Tcap * k;
+  const int32_t* topi = topi0 + (int64_t)b * Tcap * k;
   uint64_t* table = (uint64_t*)((char*)arena + L.table);
   __shared__ int c_node[2][kBeam], c_last[2][kBeam], c_depth[2][kBeam];
   __shared__ double c_pb[2][kBeam], c_pnb[2][kBeam];
@@ -146,7 +159,7 @@ __global__ __launch_bounds__(kThreads) void rescore_search_kernel(int32_t* __res
   __shared__ int s_ncur, s_err;
 
   const int tid = threadIdx.x;
-  int Tp = Tp_dev[0];
+  int Tp = Tp_dev[b];
   Tp = Tp < 0 ? 0 : (Tp > Tcap ? Tcap : Tp);
   if (tid == 0) {
     c_node[0][0] = -1;
@@ -348,15 +361,23 @@ __global__ __launch_bounds__(kThreads) void rescore_search_kernel(int32_t* __res
 }
 
 // ---- decoder inputs of the n-best (u2.py:268-298) at the static shape -------------------------
-// block (i, q): row q of hypothesis i's decoder mask, its ys_in / gather entry; the q = 0 blocks
-// also write the memory mask row.  A hypothesis that overflowed Lcap counts as empty here (the
-// caller runs the utterance again), rows >= n are empty.
-__global__ __launch_bounds__(kThreads) void rescore_prep_kernel(const int32_t* __restrict__ arena, int Tcap, int Lcap,
+// block (i, q) of grid row b: row q of hypothesis i's decoder mask, its ys_in / gather entry; the
+// q = 0 blocks also write the memory mask row: frames >= mem_len[b] masked, or >= the arena's T'
+// when mem_len is null.  A hypothesis that overflowed Lcap counts as empty here (the caller runs
+// the utterance again), rows >= n are empty.  Utterance b owns hypothesis rows [10 b, 10 b + 10).
+__global__ __launch_bounds__(kThreads) void rescore_prep_kernel(const int32_t* __restrict__ arena0, int Tcap, int Lcap,
                                                                 int sos, int eos, int32_t* __restrict__ ys_in,
                                                                 uint8_t* __restrict__ dec_mask, int dec_ld,
-                                                                int32_t* __restrict__ gidx, uint8_t* __restrict__ mem_mask) {
+                                                                int32_t* __restrict__ gidx, uint8_t* __restrict__ mem_mask,
+                                                                const int32_t* __restrict__ mem_len) {
   const Layout L = make_layout(Tcap, Lcap);
   const int L1 = Lcap + 1;
+  const int b = blockIdx.y;
+  const int32_t* arena = (const int32_t*)((const char*)arena0 + (int64_t)b * L.total);
+  ys_in += (int64_t)b * kBeam * L1;
+  dec_mask += (int64_t)b * kBeam * L1 * dec_ld;
+  gidx += (int64_t)b * kBeam * L1;
+  mem_mask += (int64_t)b * kBeam * Tcap;
   const int i = blockIdx.x / L1, q = blockIdx.x % L1;
   const int n = arena[R_N];
   int len = i < n ? arena[R_LENS + i] : 0;
@@ -369,16 +390,19 @@ __global__ __launch_bounds__(kThreads) void rescore_prep_kernel(const int32_t* _
     gidx[(int64_t)i * L1 + q] = i < n ? (q < len ? tok[q] : (q == len ? eos : -1)) : -1;
   }
   if (q == 0) {
-    const int Tp = arena[R_TP];
-    for (int t = threadIdx.x; t < Tcap; t += kThreads) mem_mask[(int64_t)i * Tcap + t] = (uint8_t)(t >= Tp);
+    const int Tm = mem_len ? mem_len[b] : arena[R_TP];
+    for (int t = threadIdx.x; t < Tcap; t += kThreads) mem_mask[(int64_t)i * Tcap + t] = (uint8_t)(t >= Tm);
   }
 }
 
 // ---- pick (u2.py:300-315, decoding.pick_best) --------------------------------------------------
-__global__ __launch_bounds__(64) void rescore_pick_kernel(int32_t* __restrict__ arena, int Tcap, int Lcap,
+// one workgroup per utterance: its arena, its [10][L1cap] block of gathered
+__global__ __launch_bounds__(64) void rescore_pick_kernel(int32_t* __restrict__ arena0, int Tcap, int Lcap,
                                                           const float* __restrict__ gathered, double ctc_weight) {
   const Layout L = make_layout(Tcap, Lcap);
   const int L1 = Lcap + 1;
+  int32_t* arena = (int32_t*)((char*)arena0 + (int64_t)blockIdx.x * L.total);
+  gathered += (int64_t)blockIdx.x * kBeam * L1;
   __shared__ float tot[kBeam];
   __shared__ int s_best;
   const int n = min(max(arena[R_N], 0), kBeam);
@@ -417,13 +441,57 @@ __global__ __launch_bounds__(64) void rescore_pick_kernel(int32_t* __restrict__ 
   }
 }
 
-int check_arena(const void* arena, int64_t arena_bytes, int Tcap, int Lcap, const char* who) {
+constexpr int kMaxBatch = 4096;
+
+int check_arena(const void* arena, int64_t arena_bytes, int B, int Tcap, int Lcap, const char* who) {
   LASR_CHECK_ARG(arena != nullptr, "%s: null arena", who);
+  LASR_CHECK_ARG(B >= 1 && B <= kMaxBatch, "%s: B = %d outside [1, %d]", who, B, kMaxBatch);
   LASR_CHECK_ARG(Tcap >= 1 && Tcap <= (1 << 16), "%s: Tcap = %d outside [1, 65536]", who, Tcap);
   LASR_CHECK_ARG(Lcap >= 1 && Lcap <= (1 << 16), "%s: Lcap = %d outside [1, 65536]", who, Lcap);
   LASR_CHECK_ARG(((uintptr_t)arena & 255) == 0, "%s: arena must be 256-B aligned", who);
-  LASR_CHECK_ARG(arena_bytes >= make_layout(Tcap, Lcap).total, "%s: arena too small", who);
+  LASR_CHECK_ARG(arena_bytes >= (int64_t)B * make_layout(Tcap, Lcap).total, "%s: arena too small", who);
   return LASR_OK;
+}
+
+int search(const char* who, void* arena, int64_t arena_bytes, int B, int Tcap, int Lcap, int k, int blank, int beam,
+           const float* topk_val, const int32_t* topk_idx, const int32_t* Tp_dev, void* stream) {
+  int rc = check_arena(arena, arena_bytes, B, Tcap, Lcap, who);
+  if (rc) return rc;
+  LASR_CHECK_ARG(beam == kBeam, "%s: only the reference's beam of 10 is built (got %d)", who, beam);
+  LASR_CHECK_ARG(k >= 1 && k <= kBeam, "%s: k = %d outside [1, 10]", who, k);
+  LASR_CHECK_ARG(blank >= 0, "%s: blank = %d", who, blank);
+  LASR_CHECK_ARG(topk_val && topk_idx && Tp_dev, "%s: null inputs", who);
+  const Layout L = make_layout(Tcap, Lcap);
+  hipStream_t st = (hipStream_t)stream;
+  // table_cap is a power of two >= 1024: two keys per thread, no tail
+  const unsigned clear_blocks = (unsigned)(L.table_cap / 2 / 256);
+  rescore_clear_kernel<<<dim3(clear_blocks, B), 256, 0, st>>>((char*)arena + L.table, L.total);
+  int rc2 = lasr_check_launch("rescore_clear");
+  if (rc2) return rc2;
+  rescore_search_kernel<<<B, kThreads, 0, st>>>((int32_t*)arena, Tcap, Lcap, k, blank, topk_val, topk_idx, Tp_dev);
+  return lasr_check_launch("rescore_search");
+}
+
+int prep(const char* who, const void* arena, int64_t arena_bytes, int B, int Tcap, int Lcap, int sos, int eos,
+         int32_t* ys_in, uint8_t* dec_mask, int dec_ld, int32_t* gather_idx, uint8_t* mem_mask, const int32_t* mem_len,
+         void* stream) {
+  int rc = check_arena(arena, arena_bytes, B, Tcap, Lcap, who);
+  if (rc) return rc;
+  LASR_CHECK_ARG(ys_in && dec_mask && gather_idx && mem_mask, "%s: null outputs", who);
+  LASR_CHECK_ARG(dec_ld >= Lcap + 1, "%s: dec_ld = %d < L1cap = %d", who, dec_ld, Lcap + 1);
+  LASR_CHECK_ARG(sos >= 0 && eos >= 0, "%s: sos / eos", who);
+  rescore_prep_kernel<<<dim3(kBeam * (Lcap + 1), B), kThreads, 0, (hipStream_t)stream>>>(
+      (const int32_t*)arena, Tcap, Lcap, sos, eos, ys_in, dec_mask, dec_ld, gather_idx, mem_mask, mem_len);
+  return lasr_check_launch("rescore_prep");
+}
+
+int pick(const char* who, void* arena, int64_t arena_bytes, int B, int Tcap, int Lcap, const float* gathered,
+         double ctc_weight, void* stream) {
+  int rc = check_arena(arena, arena_bytes, B, Tcap, Lcap, who);
+  if (rc) return rc;
+  LASR_CHECK_ARG(gathered != nullptr, "%s: null gathered", who);
+  rescore_pick_kernel<<<B, 64, 0, (hipStream_t)stream>>>((int32_t*)arena, Tcap, Lcap, gathered, ctc_weight);
+  return lasr_check_launch("rescore_pick");
 }
 
 }  // namespace
@@ -433,44 +501,46 @@ extern "C" int64_t lasr_rescore_workspace(int Tcap, int Lcap) {
   return make_layout(Tcap, Lcap).total;
 }
 
+extern "C" int64_t lasr_rescore_workspace_batch(int B, int Tcap, int Lcap) {
+  if (B <= 0 || B > kMaxBatch) return 0;
+  return (int64_t)B * lasr_rescore_workspace(Tcap, Lcap);
+}
+
 extern "C" int lasr_rescore_search(void* arena, int64_t arena_bytes, int Tcap, int Lcap, int k, int blank, int beam,
                                    const float* topk_val, const int32_t* topk_idx, const int32_t* Tp_dev,
                                    void* stream) {
-  int rc = check_arena(arena, arena_bytes, Tcap, Lcap, "lasr_rescore_search");
-  if (rc) return rc;
-  LASR_CHECK_ARG(beam == kBeam, "lasr_rescore_search: only the reference's beam of 10 is built (got %d)", beam);
-  LASR_CHECK_ARG(k >= 1 && k <= kBeam, "lasr_rescore_search: k = %d outside [1, 10]", k);
-  LASR_CHECK_ARG(blank >= 0, "lasr_rescore_search: blank = %d", blank);
-  LASR_CHECK_ARG(topk_val && topk_idx && Tp_dev, "lasr_rescore_search: null inputs");
-  const Layout L = make_layout(Tcap, Lcap);
-  hipStream_t st = (hipStream_t)stream;
-  // table_cap is a power of two >= 1024: two keys per thread, no tail
-  const unsigned clear_blocks = (unsigned)(L.table_cap / 2 / 256);
-  rescore_clear_kernel<<<clear_blocks, 256, 0, st>>>((uint4*)((char*)arena + L.table));
-  int rc2 = lasr_check_launch("rescore_clear");
-  if (rc2) return rc2;
-  rescore_search_kernel<<<1, kThreads, 0, st>>>((int32_t*)arena, Tcap, Lcap, k, blank, topk_val, topk_idx, Tp_dev);
-  return lasr_check_launch("rescore_search");
+  return search("lasr_rescore_search", arena, arena_bytes, 1, Tcap, Lcap, k, blank, beam, topk_val, topk_idx, Tp_dev,
+                stream);
+}
+
+extern "C" int lasr_rescore_search_batch(void* arena, int64_t arena_bytes, int B, int Tcap, int Lcap, int k, int blank,
+                                         int beam, const float* topk_val, const int32_t* topk_idx,
+                                         const int32_t* Tp_dev, void* stream) {
+  return search("lasr_rescore_search_batch", arena, arena_bytes, B, Tcap, Lcap, k, blank, beam, topk_val, topk_idx,
+                Tp_dev, stream);
 }
 
 extern "C" int lasr_rescore_prep(const void* arena, int64_t arena_bytes, int Tcap, int Lcap, int sos, int eos,
                                  int32_t* ys_in, uint8_t* dec_mask, int dec_ld, int32_t* gather_idx,
                                  uint8_t* mem_mask, void* stream) {
-  int rc = check_arena(arena, arena_bytes, Tcap, Lcap, "lasr_rescore_prep");
-  if (rc) return rc;
-  LASR_CHECK_ARG(ys_in && dec_mask && gather_idx && mem_mask, "lasr_rescore_prep: null outputs");
-  LASR_CHECK_ARG(dec_ld >= Lcap + 1, "lasr_rescore_prep: dec_ld = %d < L1cap = %d", dec_ld, Lcap + 1);
-  LASR_CHECK_ARG(sos >= 0 && eos >= 0, "lasr_rescore_prep: sos / eos");
-  rescore_prep_kernel<<<kBeam * (Lcap + 1), kThreads, 0, (hipStream_t)stream>>>(
-      (const int32_t*)arena, Tcap, Lcap, sos, eos, ys_in, dec_mask, dec_ld, gather_idx, mem_mask);
-  return lasr_check_launch("rescore_prep");
+  return prep("lasr_rescore_prep", arena, arena_bytes, 1, Tcap, Lcap, sos, eos, ys_in, dec_mask, dec_ld, gather_idx,
+              mem_mask, nullptr, stream);
+}
+
+extern "C" int lasr_rescore_prep_batch(const void* arena, int64_t arena_bytes, int B, int Tcap, int Lcap, int sos,
+                                       int eos, int32_t* ys_in, uint8_t* dec_mask, int dec_ld, int32_t* gather_idx,
+                                       uint8_t* mem_mask, const int32_t* mem_len, void* stream) {
+  LASR_CHECK_ARG(mem_len != nullptr, "lasr_rescore_prep_batch: null mem_len");
+  return prep("lasr_rescore_prep_batch", arena, arena_bytes, B, Tcap, Lcap, sos, eos, ys_in, dec_mask, dec_ld,
+              gather_idx, mem_mask, mem_len, stream);
 }
 
 extern "C" int lasr_rescore_pick(void* arena, int64_t arena_bytes, int Tcap, int Lcap, const float* gathered,
                                  double ctc_weight, void* stream) {
-  int rc = check_arena(arena, arena_bytes, Tcap, Lcap, "lasr_rescore_pick");
-  if (rc) return rc;
-  LASR_CHECK_ARG(gathered != nullptr, "lasr_rescore_pick: null gathered");
-  rescore_pick_kernel<<<1, 64, 0, (hipStream_t)stream>>>((int32_t*)arena, Tcap, Lcap, gathered, ctc_weight);
-  return lasr_check_launch("rescore_pick");
+  return pick("lasr_rescore_pick", arena, arena_bytes, 1, Tcap, Lcap, gathered, ctc_weight, stream);
+}
+
+extern "C" int lasr_rescore_pick_batch(void* arena, int64_t arena_bytes, int B, int Tcap, int Lcap,
+                                       const float* gathered, double ctc_weight, void* stream) {
+  return pick("lasr_rescore_pick_batch", arena, arena_bytes, B, Tcap, Lcap, gathered, ctc_weight, stream);
 }

@@ -386,8 +386,212 @@ def attention_rescore_device(model, x, trace=None, encoder_graph=True):
     return tuple(head[off["best"]:off["best"] + blen].tolist())
 
 
+# ================================================== attention rescoring, batched ===
+# One group's attention logits, 10 n (Lcap + 1) V elements, are the largest buffer of the pass:
+# 352 MB in fp32 for all of B 32 at Lcap 64, V 4233, and 1.4 GB at Lcap 256.  The decoder pass
+# runs over groups of utterances whose logits stay under this many bytes.  The logits are written
+# once by the output projection and read once by the log-softmax gather, so half of the 256 MB
+# Infinity Cache keeps that hand-off on chip with room for the memory and the weights; and the
+# graph pool of every cached state then holds one group's logits, not Bcap's.  (Reasoned, not
+# tuned: the pass is bounded by the serial search)
+_LOGITS_BUDGET_BYTES = 128 << 20
+
+
+def _pow2_cap(n):
+    c = 64
+    while c < n:
+        c *= 2
+    return c
+
+
+class _RescoreBatch:
+    """Batch arena, static buffers and the captured graph of one model at one (Bcap, Tcap, Lcap).
+    Utterance b owns arena b, memory row b and the hypothesis rows [10 b, 10 b + 10)."""
+
+    def __init__(self, model, Bcap, Tcap, Lcap, d, adt, dev):
+        self.Bcap, self.Tcap, self.Lcap, self.L1 = Bcap, Tcap, Lcap, Lcap + 1
+        self.k = min(_BEAM, model.vocab_size)
+        self.off = rescore_layout(Tcap, Lcap)
+        self.stride = K.rescore_workspace(Tcap, Lcap)
+        self.arena = torch.zeros(K.rescore_workspace_batch(Bcap, Tcap, Lcap), dtype=torch.uint8, device=dev)
+        self.mem = torch.zeros(Bcap, Tcap, d, dtype=adt, device=dev)
+        self.tp = torch.zeros(Bcap, dtype=torch.int32, device=dev)
+        self.mem_len = torch.ones(Bcap, dtype=torch.int32, device=dev)
+        L1, R = self.L1, _BEAM * Bcap
+        self.ys_in = torch.zeros(R, L1, dtype=torch.int32, device=dev)
+        self.dec_mask = torch.ones(R, L1, (L1 + 15) // 16 * 16, dtype=torch.uint8, device=dev)[:, :, :L1]
+        self.gidx = torch.full((R * L1,), -1, dtype=torch.int32, device=dev)
+        self.mem_mask = torch.ones(R, Tcap, dtype=torch.uint8, device=dev)
+        self.gathered = torch.zeros(R * L1, dtype=torch.float32, device=dev)
+        # the decoder groups: as few as the budget allows, of equal size (static per state)
+        row_bytes = _BEAM * L1 * ((model.vocab_size + 7) // 8 * 8) * self.mem.element_size()  # one utterance's
+        ngroups = -(-Bcap // max(1, _LOGITS_BUDGET_BYTES // row_bytes))
+        size = -(-Bcap // ngroups)
+        self.groups = [(a, min(a + size, Bcap)) for a in range(0, Bcap, size)]
+        self.filled = (0, 0)
+        self.graph = None
+        self.keep = None
+
+    def launches(self, model):
+        """ctc_lo + log-softmax top-k over all Bcap Tcap rows, the batched search, the decoder
+        inputs, then per group the decoder at (10 n, L1cap, Tcap) under the memory mask and the
+        gather, and the pick: one stream, in this order."""
+        Bcap, Tcap, Lcap, L1 = self.Bcap, self.Tcap, self.Lcap, self.L1
+        d = self.mem.shape[2]
+        logits = DN.ctc_logits(self.mem.view(Bcap * Tcap, d), model)
+        vals, idx, _ = K.logsoftmax_topk(logits, self.k)
+        K.rescore_search_batch(self.arena, Bcap, Tcap, Lcap, vals, idx, self.tp, model.blank, _BEAM)
+        K.rescore_prep_batch(self.arena, Bcap, Tcap, Lcap, model.sos, model.eos, self.ys_in, self.dec_mask, self.gidx,
+                             self.mem_mask, self.mem_len)
+        for a, b in self.groups:
+            n, r0, r1 = _BEAM * (b - a), _BEAM * a, _BEAM * b
+            mem = self.mem[a:b].unsqueeze(1).expand(b - a, _BEAM, Tcap, d).reshape(n * Tcap, d)
+            h_attn = DN.decoder_logits(model, mem, self.ys_in[r0:r1], self.dec_mask[r0:r1], self.mem_mask[r0:r1], n, L1,
+                                       Tcap)
+            _, _, g = K.logsoftmax_topk(h_attn, 0, gather_idx=self.gidx[r0 * L1:r1 * L1])
+            self.gathered[r0 * L1:r1 * L1].copy_(g)
+        K.rescore_pick_batch(self.arena, Bcap, Tcap, Lcap, self.gathered, _CTC_WEIGHT)
+        return vals, idx
+
+    capture = _Rescore.capture
+
+    def run(self, model, h, pred_len, mem_len):
+        """One batch: h [B, T', d], the search lengths and memory lengths (int32 [B], device) in,
+        one replay, the B result heads out (ONE copy).  Rows >= B are inert: T' = 0 (no frame
+        is searched) and one visible frame of zero memory, so that their softmax has a key."""
+        if self.graph is None:
+            self.capture(model)
+        B, Tp = h.shape[0], h.shape[1]
+        fB, fT = self.filled
+        self.mem[:B, :Tp].copy_(h)
+        if fT > Tp:
+            self.mem[:B, Tp:fT].zero_()
+        if fB > B:
+            self.mem[B:fB, :fT].zero_()
+        self.filled = (B, Tp)
+        self.tp.zero_()
+        self.tp[:B].copy_(pred_len)
+        self.mem_len.fill_(1)
+        self.mem_len[:B].copy_(mem_len)
+        self.graph.replay()
+        heads = self.arena.view(self.Bcap, self.stride)[:B, :4 * self.off["head_words"]]
+        return heads.cpu().numpy().view(np.int32)
+
+
+def _rescore_batch_state(model, key, h):
+    """The cache of the batched states: dropped, like _rescore_state's, on a weight update or a
+    store-generation change.  key None: the hints {"bcaps": {Bcap, ...}, (Bcap, Tcap): Lcap}."""
+    st = model.store
+    ver = (st.flat._version, st.generation, h.dtype, h.shape[-1])
+    cache = model.__dict__.setdefault("_rescore_batch_states", {})
+    if cache.get("ver") != ver:
+        cache.clear()
+        cache["ver"] = ver
+        cache["hint"] = {}
+    if key is None:
+        return cache["hint"]
+    s = cache.get(key)
+    if s is None:
+        s = cache[key] = _RescoreBatch(model, *key, h.shape[-1], h.dtype, h.device)
+    return s
+
+
+def attention_rescore_batch(model, xs, xlens, trace=None):
+    """u2.py:269-317 (beam 10, ctc weight 0.5, the first strict maximum wins) for a padded batch
+    xs [B, T, F] with frame counts xlens: a list of B token tuples.
+
+    The reference has no batched inference; this composes its modules as ``U2.forward`` composes
+    them, in eval mode (the precedent of ``Paraformer.inference_batch``): the encoder runs on the
+    padded batch under padding_mask(xlens); the CTC prefix beam search of row b covers
+    ``get_pred_len(xlens)[b]`` frames; the decoder sees memory row b under the encoder's own
+    subsampled padding mask (frame t' valid iff 4 t' < xlen_b, capped at T').  So a row with
+    xlen_b == T is the computation of ``U2.inference(xs[b:b+1])``, while a padded row is the
+    computation training sees for that row (its frames next to the padding see the padding
+    through the convolutions; the memory mask is up to two frames longer than the search), not the
+    unpadded single-utterance one.  A row depends on its own padding only, never on
+    the content of another row.
+
+    After the (eager) encoder pass everything stays on the device: ONE replay of a captured
+    linear hipGraph at the static shape (Bcap, Tcap, Lcap) runs ctc_lo, the per-frame log-softmax
+    top-k, the batched search (csrc/rescore.hip, one workgroup per row), the decoder inputs, the
+    decoder at (10 n, Lcap + 1, Tcap) per group of n utterances (_LOGITS_BUDGET_BYTES), the gathers
+    and the pick, and ONE device-to-host copy brings back the B result heads.  Tcap and Lcap
+    follow attention_rescore_device (powers of two >= 64; Lcap doubles, and only the graph is
+    run again, when any row overflows; a bucket keeps the largest Lcap it has needed).  Bcap is
+    the smallest batch capacity that holds B among those used since the states were last
+    dropped, else B itself: a shorter batch (the last of a set) runs in a state of the set's
+    batch size with its spare rows inert.  States are cached per (Bcap, Tcap, Lcap) and dropped
+    on a weight update or a store-generation change.
+
+    trace (a dict) receives, as lists over the rows, what attention_rescore_device's receives:
+    "nbest", "gathered", "best", "totals"; "caps" = (Bcap, Tcap, Lcap); and "state", the
+    _RescoreBatch that ran (its ``keep`` holds the candidates the search read)."""
+    if xs.device.type != "cuda":
+        raise RuntimeError("liteasr_amd decoding runs on the HIP device only")
+    if xs.dim() != 3:
+        raise ValueError("attention_rescore_batch: xs [B, T, F]")
+    B, T = xs.shape[0], xs.shape[1]
+    lens = [int(n) for n in (xlens.tolist() if torch.is_tensor(xlens) else xlens)]
+    if len(lens) != B or B < 1:
+        raise ValueError(f"attention_rescore_batch: {len(lens)} frame counts for {B} rows")
+    for b, n in enumerate(lens):
+        if n > T:
+            raise ValueError(f"attention_rescore_batch: row {b} has {n} frames, xs holds {T}")
+        if _sub_len(n) <= 0:
+            raise ValueError(f"attention_rescore_batch: row {b}: {n} frames subsample to none")
+    dev = xs.device
+    xl = torch.tensor(lens, dtype=torch.int64, device=dev)
+    ys = torch.full((B, 1), -1, dtype=torch.int64, device=dev)
+    xe, prep, _ = model._run_encoder(xs, xl, ys, torch.zeros(B, dtype=torch.int64, device=dev))
+    Tp = prep.T
+    h = DN.encoder_out(xe, model, model.compute_dtype).view(B, Tp, -1)
+    mem_len = (prep.enc_mask == 0).sum(1, dtype=torch.int32)
+    hint = _rescore_batch_state(model, None, h)
+    bcaps = hint.setdefault("bcaps", set())
+    Bcap = min((c for c in bcaps if c >= B), default=B)
+    bcaps.add(Bcap)
+    Tcap = _pow2_cap(Tp)
+    Lcap = hint.get((Bcap, Tcap), 64)
+    while True:
+        s = _rescore_batch_state(model, (Bcap, Tcap, Lcap), h)
+        heads = s.run(model, h, prep.pred_len, mem_len)
+        errs = heads[:, _R_ERR]
+        for b in range(B):
+            if errs[b] & ~1:
+                what = _RESCORE_ERRORS.get(int(errs[b]) & ~1, f"error {int(errs[b])}")
+                raise RuntimeError(f"attention_rescore_batch: row {b}: {what}")
+        if not errs.any():
+            break
+        if Lcap >= Tcap:
+            raise RuntimeError(f"attention_rescore_batch: hypothesis longer than T' cap {Tcap}")
+        Lcap *= 2
+    hint[(Bcap, Tcap)] = Lcap
+    off = s.off
+    out = []
+    for b in range(B):
+        head = heads[b]
+        assert int(head[_R_TP]) == _sub_len(lens[b]), (b, int(head[_R_TP]), lens[b])
+        out.append(tuple(head[off["best"]:off["best"] + int(head[_R_BESTLEN])].tolist()))
+    if trace is not None:
+        for key in ("nbest", "gathered", "best", "totals"):
+            trace[key] = []
+        for b in range(B):
+            head = heads[b]
+            n = int(head[_R_N])
+            hyps = rescore_nbest(head, Lcap)
+            Lmax = max(1, max(len(t) for t, _ in hyps))
+            g = head[off["gath"]:off["gath"] + _BEAM * (Lcap + 1)].view(np.float32).reshape(_BEAM, Lcap + 1)
+            trace["nbest"].append(hyps)
+            trace["gathered"].append(g[:n, :Lmax + 1].copy())
+            trace["best"].append(int(head[_R_BEST]))
+            trace["totals"].append(head[_R_TOTAL:_R_TOTAL + n].view(np.float32).copy())
+        trace["caps"] = (Bcap, Tcap, Lcap)
+        trace["state"] = s
+    return out
+
+
 # ======================================================= transducer beam search ===
-_ERRORS = {1: "node arena full", 2: "state-slot arena full", 3: "trie hash full", 4: "non-finite joint logits",
+_ERRORS ={1: "node arena full", 2: "state-slot arena full", 3: "trie hash full", 4: "non-finite joint logits",
            5: "empty hypothesis list"}
 # ctrl words of the search arena (include/liteasr_hip.h)
 _C_ERR, _C_POPS, _C_CUR, _C_DOSTEP, _C_STEPS, _C_DONE, _C_BEST, _C_BESTLEN = 0, 1, 3, 4, 10, 11, 12, 13

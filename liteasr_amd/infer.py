@@ -25,7 +25,13 @@ Differences from the reference, on purpose:
   times in the set: a capture costs two extra encoder passes and a replay saves about 0.59 of
   one, so it pays from the fourth use.  Utterances are decoded in frame-count order, so equal
   shapes are adjacent and a captured graph is not evicted between its uses; the blocks are
-  logged in dataset order.
+  logged in dataset order;
+* ``inference.batch_size`` (default 1: the loop above, unchanged).  Above 1, models that have
+  ``inference_batch`` (U2, Paraformer) decode ``batch_plan``'s groups: utterances in frame-count
+  order, cut into consecutive groups of ``batch_size``, each zero-padded to its longest.  A padded
+  row is the computation training sees for that row, not the unpadded single-utterance one
+  (``decoding.attention_rescore_batch``), so a hypothesis may differ from ``batch_size`` 1's.
+  Models without ``inference_batch`` (Transducer) are decoded utterance by utterance.
 """
 
 import logging
@@ -64,15 +70,45 @@ def graph_plan(xlens, min_uses=GRAPH_MIN_USES):
     return order, [uses[n] >= min_uses for n in xlens]
 
 
-def infer_dataset(task, model, dataset, device):
+def batch_plan(xlens, batch_size):
+    """The groups of a batched decode: utterance indices in frame-count order (stable in dataset
+    order, ``graph_plan``'s order), cut into consecutive groups of ``batch_size``; the last may be
+    short.  Neighbours in that order differ least in length, so this pads least."""
+    if batch_size < 1:
+        raise ValueError(f"inference.batch_size must be at least 1, got {batch_size}")
+    order = sorted(range(len(xlens)), key=lambda i: xlens[i])
+    return [order[a:a + batch_size] for a in range(0, len(order), batch_size)]
+
+
+def pad_batch(xs):
+    """Utterances (features (T_i, F) or int16 PCM (n_i,)) zero-padded along their first dimension
+    to the longest, stacked: (batch, per-row lengths)."""
+    lens = [int(x.shape[0]) for x in xs]
+    out = xs[0].new_zeros((len(xs), max(lens)) + tuple(xs[0].shape[1:]))
+    for b, x in enumerate(xs):
+        out[b, :lens[b]] = x
+    return out, lens
+
+
+def infer_dataset(task, model, dataset, device, batch_size=1):
     """Decode one test set; returns (errors, reference length, hypotheses in dataset order)."""
     xlens = [dataset[i].xlen for i in range(len(dataset))]
-    order, graphed = graph_plan(xlens)
     hyps = [None] * len(dataset)
+    if batch_size > 1 and not hasattr(model, "inference_batch"):
+        logger.info("{} has no inference_batch: decoding utterance by utterance (inference.batch_size={} ignored)"
+                    .format(type(model).__name__, batch_size))
+        batch_size = 1
     with torch.no_grad():
-        for i in order:
-            feat = dataset[i].x.unsqueeze(0).to(device)
-            hyps[i] = task.inference(feat, model, encoder_graph=graphed[i])
+        if batch_size > 1:
+            for group in batch_plan(xlens, batch_size):
+                xs, lens = pad_batch([dataset[i].x for i in group])
+                for i, hyp in zip(group, task.inference_batch(xs.to(device), lens, model)):
+                    hyps[i] = hyp
+        else:
+            order, graphed = graph_plan(xlens)
+            for i in order:
+                feat = dataset[i].x.unsqueeze(0).to(device)
+                hyps[i] = task.inference(feat, model, encoder_graph=graphed[i])
     total_len = total_err = 0
     for i, hyp in enumerate(hyps):
         ref = dataset[i].text
@@ -98,7 +134,7 @@ def infer(cfg):
 
     test_sets = task.dataset("test")
     for test_set in test_sets if isinstance(test_sets, (list, tuple)) else [test_sets]:
-        infer_dataset(task, model, test_set, device)
+        infer_dataset(task, model, test_set, device, batch_size=int(cfg.inference.get("batch_size", 1) or 1))
 
 
 NEEDS = ("task.vocab", "task.test", "inference.ckpt_name", "inference.ckpt_path")

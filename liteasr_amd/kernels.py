@@ -1686,6 +1686,69 @@ def rescore_pick(arena, Tcap, Lcap, gathered, ctc_weight):
     N.call("lasr_rescore_pick", ptr(arena), arena.numel(), Tcap, Lcap, ptr(gathered), float(ctc_weight), stream())
 
 
+def rescore_workspace_batch(B, Tcap, Lcap):
+    """Bytes of the batch arena: B single-utterance arenas laid end to end, stride
+    rescore_workspace(Tcap, Lcap) (lasr_rescore_workspace_batch)."""
+    return int(N.load().lasr_rescore_workspace_batch(int(B), int(Tcap), int(Lcap)))
+
+
+def _rescore_arena_batch(arena, B, Tcap, Lcap, who, *others):
+    need = rescore_workspace_batch(B, Tcap, Lcap)
+    if B < 1 or need == 0:
+        raise ValueError(f"{who}: B = {B} is not a batch the kernels take")
+    if arena.dtype != torch.uint8 or not arena.is_contiguous() or arena.numel() < need:
+        raise ValueError(f"{who}: arena must be contiguous uint8 of rescore_workspace_batch(B, Tcap, Lcap) bytes")
+    if not arena.is_cuda or any(t.device != arena.device for t in others):
+        raise ValueError(f"{who}: the arena and every tensor must be on the same HIP device")
+
+
+def rescore_search_batch(arena, B, Tcap, Lcap, vals, idx, tp_dev, blank, beam=10):
+    """B CTC prefix beam searches in one launch (lasr_rescore_search_batch): utterance b reads the
+    candidates vals / idx [b Tcap, (b + 1) Tcap) of [>= B Tcap, k] and T' = tp_dev[b] (int32 [>= B]
+    on the device) and writes arena b of the batch arena."""
+    _rescore_arena_batch(arena, B, Tcap, Lcap, "rescore_search_batch", vals, idx, tp_dev)
+    if vals.dtype != torch.float32 or idx.dtype != torch.int32 or vals.shape != idx.shape or vals.dim() != 2 \
+            or not vals.is_contiguous() or not idx.is_contiguous():
+        raise ValueError("rescore_search_batch: vals f32 / idx i32, contiguous [rows, k]")
+    if vals.shape[0] < B * Tcap:
+        raise ValueError(f"rescore_search_batch: {vals.shape[0]} candidate rows < B Tcap = {B * Tcap}")
+    if tp_dev.dtype != torch.int32 or tp_dev.numel() < B or not tp_dev.is_contiguous():
+        raise ValueError("rescore_search_batch: tp_dev must be B contiguous int32 device words")
+    N.call("lasr_rescore_search_batch", ptr(arena), arena.numel(), B, Tcap, Lcap, vals.shape[1], int(blank),
+           int(beam), ptr(vals), ptr(idx), ptr(tp_dev), stream())
+
+
+def rescore_prep_batch(arena, B, Tcap, Lcap, sos, eos, ys_in, dec_mask, gather_idx, mem_mask, mem_len):
+    """Decoder inputs of the B n-bests (lasr_rescore_prep_batch): ys_in i32 [10 B, L1cap], dec_mask
+    u8 [10 B, L1cap, >= L1cap] (row stride = its stride(1)), gather_idx i32 [10 B L1cap], mem_mask
+    u8 [10 B, Tcap]; utterance b owns rows [10 b, 10 b + 10), and its memory mask is 1 at frames
+    >= mem_len[b] (int32 [B] on the device)."""
+    _rescore_arena_batch(arena, B, Tcap, Lcap, "rescore_prep_batch", ys_in, dec_mask, gather_idx, mem_mask, mem_len)
+    L1, R = Lcap + 1, 10 * B
+    ld = dec_mask.stride(1)
+    if (ys_in.dtype != torch.int32 or tuple(ys_in.shape) != (R, L1) or not ys_in.is_contiguous()
+            or gather_idx.dtype != torch.int32 or gather_idx.numel() != R * L1 or not gather_idx.is_contiguous()
+            or mem_mask.dtype != torch.uint8 or tuple(mem_mask.shape) != (R, Tcap) or not mem_mask.is_contiguous()
+            or dec_mask.dtype != torch.uint8 or tuple(dec_mask.shape[:2]) != (R, L1) or dec_mask.shape[2] < L1
+            or dec_mask.stride(2) != 1 or dec_mask.stride(0) != L1 * ld or ld < L1
+            or mem_len.dtype != torch.int32 or mem_len.numel() != B or not mem_len.is_contiguous()):
+        raise ValueError("rescore_prep_batch: output shapes / dtypes")
+    if R * L1 * ld > dec_mask.untyped_storage().nbytes() - dec_mask.storage_offset():
+        raise ValueError("rescore_prep_batch: dec_mask rows walk past its storage")
+    N.call("lasr_rescore_prep_batch", ptr(arena), arena.numel(), B, Tcap, Lcap, int(sos), int(eos), ptr(ys_in),
+           ptr(dec_mask), ld, ptr(gather_idx), ptr(mem_mask), ptr(mem_len), stream())
+
+
+def rescore_pick_batch(arena, B, Tcap, Lcap, gathered, ctc_weight):
+    """Best hypothesis of each utterance from the gathered attention log-probs f32 [10 B L1cap]
+    (lasr_rescore_pick_batch)."""
+    _rescore_arena_batch(arena, B, Tcap, Lcap, "rescore_pick_batch", gathered)
+    if gathered.dtype != torch.float32 or gathered.numel() != 10 * B * (Lcap + 1) or not gathered.is_contiguous():
+        raise ValueError("rescore_pick_batch: gathered must be contiguous f32 [10 B (Lcap + 1)]")
+    N.call("lasr_rescore_pick_batch", ptr(arena), arena.numel(), B, Tcap, Lcap, ptr(gathered), float(ctc_weight),
+           stream())
+
+
 # ------------------------------------------------------------------ wav2vec 2.0 ---
 def w2v_conv0_fwd(x, w, bias, k, s, y):
     """Extractor layer 0 (lasr_w2v_conv0_fwd): x [B, T_in] fp32 -> y [B, T_out, C] fp32."""

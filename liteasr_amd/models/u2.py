@@ -147,6 +147,16 @@ class U2(FusedEncoderModel):
         return self.attention_rescore(x, encoder_graph=encoder_graph)
 
     @torch.no_grad()
+    def inference_batch(self, xs, xlens):
+        """Attention rescoring (u2.py:269-317) of a padded batch xs [B, T, F] with frame counts
+        xlens, everything after the encoder on the device: a list of B token tuples.  The
+        reference's modules composed as ``forward`` composes them, in eval mode: a row with
+        xlen == T is the computation of ``inference(xs[b:b+1])``; a padded row is the computation
+        training sees for that row, not the unpadded single-utterance one
+        (decoding.attention_rescore_batch)."""
+        return D.attention_rescore_batch(self, xs, xlens)
+
+    @torch.no_grad()
     def attention(self, x):
         """liteasr/models/u2.py:163-216 (beam 10); returns the best hypothesis incl. sos."""
         return D.attention_beam_search(self, x, beam=10)

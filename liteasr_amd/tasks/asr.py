@@ -111,5 +111,19 @@ class ASRTask(LiteasrTask):
         tokens = self.vocab.lookupi(ids, convert=True)
         return "".join(tokens) if self.cfg.delimiter is None else self.cfg.delimiter.join(tokens)
 
+    def inference_batch(self, xs, xlens, model):
+        """One string per row through ``model.inference_batch`` (U2, Paraformer).  ``xs``: (B, T, F)
+        features zero-padded past ``xlens`` frames, or (B, S) int16 PCM zero-padded past ``xlens``
+        samples, which goes through the task's front end with per-row frame counts first."""
+        if xs.dtype == torch.int16:
+            frames = [num_frames(int(n)) for n in xlens]
+            xs = self.frontend(xs, torch.tensor(frames, dtype=torch.int32, device=xs.device), max_frames=max(frames))
+            xlens = frames
+        out = []
+        for ids in model.inference_batch(xs, xlens):
+            tokens = self.vocab.lookupi(list(ids), convert=True)
+            out.append("".join(tokens) if self.cfg.delimiter is None else self.cfg.delimiter.join(tokens))
+        return out
+
     def save_model(self, model_name: str, model):
         model.save(os.sep.join((self.save_dir, model_name)))
