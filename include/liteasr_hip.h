@@ -291,6 +291,30 @@ int lasr_ctc_bwd(const void* logits, int ldt, int B, int T, int V, int64_t ld, c
                  const float* lp, const float* alpha, const float* nll, float* beta,
                  int beta_ready, void* grad, int gdt, float gscale, const float* gdev, void* stream);
 
+/* CTC forced alignment (csrc/ctc_align.hip): the best path of the extended-label lattice and
+ * its backtrace, from the lp [B][T][Lmax+1] that lasr_ctc_fwd's first stage (alpha == NULL)
+ * leaves behind; targets / ilen / tlen as there (blank = 0, 2*Lmax+1 <= 1024).  fp32 scores:
+ *   v_0(0) = lp[0][blank], v_0(1) = lp[0][y_1], every other state -inf;
+ *   v_t(s) = best + lp[t][e(s)], best = v_{t-1}(s) (move 0), replaced by v_{t-1}(s-1) (move 1)
+ *   only if strictly greater, then by v_{t-1}(s-2) (move 2) only if strictly greater and s is
+ *   odd, s >= 2 and label(s) != label(s-2).
+ * End state (Tb = ilen[b], S = 2 tlen[b] + 1): S-1 if v_{Tb-1}(S-1) >= v_{Tb-1}(S-2), else
+ * S-2; state 0 for S = 1.  score [B] fp32 is its value.
+ *   states [B][T] int32: the extended state of frame t < Tb, -1 for t >= Tb;
+ *   spans  [B][Lmax][2] int32: (first frame, one past the last frame) of target i's odd state,
+ *          (-1, -1) for i >= tlen[b].
+ * Tb <= 0: score 0 for an empty target, else -inf, and only -1s.  A score that is not finite
+ * (Tb < tlen[b] + adjacent repeats, or non-finite lp): score as computed, states / spans of the
+ * row all -1.  lp rows t >= Tb are never read; ilen / tlen beyond T / Lmax are clamped.
+ * Moves are kept 2 bits each, one dword per state and 16 frames: W = ceil(T / 16) dwords per
+ * state.  When 4 (2 Lmax + 1) (2 + W) <= 65536 bytes they stay in LDS and
+ * lasr_ctc_align_workspace is 0; otherwise they are spilled to `workspace`,
+ * lasr_ctc_align_workspace = 4 B W (2 Lmax + 1) bytes (0 for sizes lasr_ctc_align refuses). */
+int lasr_ctc_align(int B, int T, int Lmax, const int32_t* targets, const int32_t* ilen,
+                   const int32_t* tlen, const float* lp, void* workspace, int64_t ws_bytes,
+                   int32_t* states, int32_t* spans, float* score, void* stream);
+int64_t lasr_ctc_align_workspace(int B, int T, int Lmax);
+
 /* ------------------------------------------------------------------------
  * Label-smoothed KL (liteasr/criterions/hybrid_ctc_attn.py:49-64):
  *   row loss = sum_c td_c (log td_c - log_softmax(h)_c), td = s/(V-1), 1-s at target;

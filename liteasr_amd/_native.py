@@ -168,6 +168,8 @@ SIGNATURES = {
     "lasr_branch_grad": [_p, _i, _l, _p, _i, _f, _f, _u, _p],
     "lasr_ctc_fwd": [_p, _i, _i, _i, _i, _l, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p],
     "lasr_ctc_lattice": [_i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p],
+    "lasr_ctc_align": [_i, _i, _i, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p],
+    "lasr_ctc_align_workspace": [_i, _i, _i],
     "lasr_rnnt_fwd": [_p, _i, _i, _i, _i, _i, _l, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p],
     "lasr_rnnt_bwd": [_p, _i, _i, _i, _i, _i, _l, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p, _i, _f, _p, _p],
     "lasr_joint_fwd": [_p, _p, _i, _i, _i, _i, _p, _i, _p],
@@ -257,7 +259,7 @@ SIGNATURES = {
 }
 _RESTYPES = {"lasr_last_error": C.c_char_p, "lasr_spec_augment_ws_bytes": C.c_int64,
              "lasr_rnnt_search_workspace": C.c_int64, "lasr_rescore_workspace": C.c_int64,
-             "lasr_rescore_workspace_batch": C.c_int64,
+             "lasr_rescore_workspace_batch": C.c_int64, "lasr_ctc_align_workspace": C.c_int64,
              "lasr_conv2_dx_w1_workspace": C.c_int64, "lasr_attn_split_work": C.c_int64,
              "lasr_dropout_scale": C.c_float, "lasr_gemm_phased_launches": C.c_int64}
 

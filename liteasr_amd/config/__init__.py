@@ -92,6 +92,8 @@ class InferenceConfig(LiteasrDataclass):
     thread_num: int = field(default=32)
     # liteasr_amd extension: utterances decoded per model.inference_batch call (1: one at a time)
     batch_size: int = field(default=1)
+    # liteasr_amd extension: where liteasr_amd.align writes <set name>.ctm / .scores (under the run dir)
+    align_dir: str = field(default="align")
 
 
 @dataclass

@@ -57,6 +57,7 @@ class AudioFileDataset(LiteasrDataset):
             raise NotImplementedError("memory_save (pickled batch dumps) is not supported")
         self.split = split
         self.data: List[Audio] = []
+        self.uttids: List[str] = []  # the utterance id of self.data[i] (the records do not carry it)
         self.batchify_policy = None
         self.postprocess = None
         if postprocess_cfg is not None:
@@ -77,6 +78,7 @@ class AudioFileDataset(LiteasrDataset):
                 assert uttid_t == uttid
                 if not self.wav:
                     self.data.append(Audio(fd, start, shape, ids, text if keep_raw else None))
+                    self.uttids.append(uttid)
                 elif ratio is not None:
                     p, q = ratio
                     samples = resampled_samples(shape, p, q)
@@ -85,10 +87,12 @@ class AudioFileDataset(LiteasrDataset):
                     else:
                         self.data.append(SpeedWavAudio(fd, start, shape, ids, text if keep_raw else None,
                                                        num_frames(samples), (p, q), samples))
+                        self.uttids.append(uttid)
                 elif num_frames(shape) == 0:
                     short += 1
                 else:
                     self.data.append(WavAudio(fd, start, shape, ids, text if keep_raw else None, num_frames(shape)))
+                    self.uttids.append(uttid)
         if short:
             logger.warning("{}: dropped {} utterance(s) shorter than one 25 ms frame".format(data_dir, short))
         self.feat_dim = int(num_mel_bins) if self.wav else self.data[0].x.shape[-1]

@@ -590,6 +590,73 @@ def attention_rescore_batch(model, xs, xlens, trace=None):
     return out
 
 
+# ============================================================= CTC forced alignment ===
+def ctc_align(model, xs, xlens, ys, ylens, trace=None):
+    """Viterbi alignment of the transcripts ys [B, L] (padded with -1 as in training, ylens
+    tokens each) to the padded batch xs [B, T, F] with frame counts xlens, through the CTC head.
+
+    Composed as ``attention_rescore_batch`` composes its encoder pass, in eval mode: the encoder
+    runs on the padded batch under padding_mask(xlens), and row b's lattice covers
+    ``get_pred_len(xlens)[b]`` encoder frames.  Then ctc_lo, the first stage of the CTC loss
+    (``K.ctc_fwd(..., alpha=None)``: the log-softmax and the gather of the blank / target
+    log-probs) and ``K.ctc_align`` (csrc/ctc_align.hip), and ONE device-to-host copy of (states,
+    spans, score).  So a row with xlen_b == T is the unpadded computation of that utterance alone,
+    while a padded row is the computation training sees for that row (the documented convention of
+    ``inference_batch``): its frames next to the padding see the padding through the convolutions.
+
+    Returns one record per row, ``{"score": float, "states": [Tb ints], "spans": [(first, end)] *
+    L_b}`` in encoder frames (``states`` the extended-lattice state of each frame, ``spans`` the
+    first frame and one past the last frame of each token), or None for a row whose score is not
+    finite (more tokens, counting a blank between adjacent repeats, than encoder frames).
+
+    trace (a dict) receives "lp", "targets", "pred_len", "ylen" (the device tensors the kernel
+    read) and "d2h", the number of device-to-host copies made (1)."""
+    if xs.device.type != "cuda":
+        raise RuntimeError("liteasr_amd decoding runs on the HIP device only")
+    if xs.dim() != 3 or ys.dim() != 2 or ys.shape[0] != xs.shape[0]:
+        raise ValueError("ctc_align: xs [B, T, F] and ys [B, L]")
+    if model.training:
+        raise RuntimeError("ctc_align: call it on a model in eval mode (model.eval())")
+    B, T = xs.shape[0], xs.shape[1]
+    lens = [int(n) for n in (xlens.tolist() if torch.is_tensor(xlens) else xlens)]
+    ylen = [int(n) for n in (ylens.tolist() if torch.is_tensor(ylens) else ylens)]
+    if len(lens) != B or len(ylen) != B or B < 1:
+        raise ValueError(f"ctc_align: {len(lens)} frame counts and {len(ylen)} token counts for {B} rows")
+    for b, (n, l) in enumerate(zip(lens, ylen)):
+        if n > T or _sub_len(n) <= 0:
+            raise ValueError(f"ctc_align: row {b} has {n} frames, xs holds {T} (and at least 7 are needed)")
+        if not 0 <= l <= ys.shape[1]:
+            raise ValueError(f"ctc_align: row {b} has {l} tokens, ys holds {ys.shape[1]}")
+    dev = xs.device
+    if ys.shape[1] == 0:  # the bookkeeping kernel wants a column
+        ys = torch.full((B, 1), -1, dtype=torch.int64, device=dev)
+    xl = torch.tensor(lens, dtype=torch.int64, device=dev)
+    yl = torch.tensor(ylen, dtype=torch.int64, device=dev)
+    with torch.no_grad():
+        xe, prep, _ = model._run_encoder(xs, xl, ys.to(dev), yl)
+        Tp, L = prep.T, prep.L
+        h = DN.encoder_out(xe, model, model.compute_dtype)
+        hc = DN.ctc_logits(h, model).view(B, Tp, -1)
+        lse = torch.empty(B * Tp, dtype=torch.float32, device=dev)
+        lp = torch.empty(B, Tp, L + 1, dtype=torch.float32, device=dev)
+        K.ctc_fwd(hc, prep.tgt_ctc, prep.pred_len, prep.ylen, lse, lp, None, None)
+        states, spans, score = K.ctc_align(lp, prep.tgt_ctc, prep.pred_len, prep.ylen)
+        # one copy: the three outputs side by side as int32 words
+        packed = torch.cat([states, spans.view(B, 2 * L), score.view(torch.int32).view(B, 1)], dim=1).cpu().numpy()
+    st, sp, sc = packed[:, :Tp], packed[:, Tp:Tp + 2 * L].reshape(B, L, 2), packed[:, Tp + 2 * L].view(np.float32)
+    out = []
+    for b in range(B):
+        if not np.isfinite(sc[b]):
+            out.append(None)
+            continue
+        Tb = _sub_len(lens[b])
+        out.append({"score": float(sc[b]), "states": st[b, :Tb].tolist(),
+                    "spans": [tuple(p) for p in sp[b, :ylen[b]].tolist()]})
+    if trace is not None:
+        trace.update(lp=lp, targets=prep.tgt_ctc, pred_len=prep.pred_len, ylen=prep.ylen, d2h=1)
+    return out
+
+
 # ======================================================= transducer beam search ===
 _ERRORS ={1: "node arena full", 2: "state-slot arena full", 3: "trie hash full", 4: "non-finite joint logits",
            5: "empty hypothesis list"}

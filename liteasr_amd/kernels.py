@@ -808,6 +808,49 @@ def ctc_bwd(logits, targets, ilen, tlen, lse, lp, alpha, nll, beta, grad, gscale
            dt(grad), gscale, ptr(gdev), stream())
 
 
+# CTC forced alignment (csrc/ctc_align.hip).  A move takes 2 bits: one dword per lattice state and
+# 16 frames.  The score vectors and every move word of the launch's T x (2 Lmax + 1) lattice stay
+# in LDS when they fit 64 KB; otherwise the words are spilled to the workspace.
+CTC_ALIGN_FRAMES_PER_WORD = 16
+CTC_ALIGN_LDS = 64 * 1024
+
+
+def ctc_align_workspace(B, T, Lmax):
+    """Bytes of workspace ``ctc_align`` needs (0: the moves stay in LDS); the formula of
+    lasr_ctc_align_workspace restated, and held to it."""
+    S = 2 * Lmax + 1
+    words = -(-T // CTC_ALIGN_FRAMES_PER_WORD)
+    if B <= 0 or T <= 0 or Lmax < 0 or S > 1024 or 4 * S * (2 + words) <= CTC_ALIGN_LDS:
+        need = 0
+    else:
+        need = 4 * B * words * S
+    native = N.load().lasr_ctc_align_workspace(B, T, Lmax)
+    assert need == native, f"ctc_align_workspace({B}, {T}, {Lmax}): {need} here, {native} in the library"
+    return need
+
+
+def ctc_align(lp, targets, ilen, tlen):
+    """Viterbi alignment of every row (lasr_ctc_align): ``lp`` fp32 (B, T, Lmax + 1) as ``ctc_fwd``
+    with ``alpha=None`` leaves it, ``targets`` int32 (B, Lmax), ``ilen`` / ``tlen`` int32 (B,).
+    Returns ``(states, spans, score)``: int32 (B, T), int32 (B, Lmax, 2) and fp32 (B,) on the
+    device; -1 past a row's lengths and in every entry of a row whose score is not finite."""
+    if lp.dtype != torch.float32 or lp.dim() != 3 or not lp.is_contiguous():
+        raise TypeError("ctc_align: lp must be a contiguous fp32 (B, T, Lmax + 1) tensor")
+    B, T, L1 = lp.shape
+    Lmax = L1 - 1
+    for name, t, shape in (("targets", targets, (B, Lmax)), ("ilen", ilen, (B,)), ("tlen", tlen, (B,))):
+        if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != lp.device:
+            raise TypeError(f"ctc_align: {name} must be a contiguous int32 {shape} tensor on the device of lp")
+    states = torch.empty(B, T, dtype=torch.int32, device=lp.device)
+    spans = torch.empty(B, Lmax, 2, dtype=torch.int32, device=lp.device)
+    score = torch.empty(B, dtype=torch.float32, device=lp.device)
+    need = ctc_align_workspace(B, T, Lmax)
+    ws = WS.get((need + 3) // 4, lp.device) if need else None
+    N.call("lasr_ctc_align", B, T, Lmax, ptr(targets), ptr(ilen), ptr(tlen), ptr(lp), ptr(ws), need, ptr(states),
+           ptr(spans), ptr(score), stream())
+    return states, spans, score
+
+
 def lsm_kl_fwd(logits, target, ignore, smoothing, lse, loss_rows):
     R, V = logits.shape
     N.call("lasr_lsm_kl_fwd", ptr(logits), dt(logits), R, V, _rows_ld(logits, 0), ptr(target), ignore,

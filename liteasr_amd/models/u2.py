@@ -156,6 +156,18 @@ class U2(FusedEncoderModel):
         (decoding.attention_rescore_batch)."""
         return D.attention_rescore_batch(self, xs, xlens)
 
+    # frames of the input per encoder frame: Conv2DLayer's two stride-2 convolutions
+    frame_subsampling = 4
+
+    @torch.no_grad()
+    def align(self, xs, xlens, ys, ylens):
+        """CTC forced alignment of the transcripts ys [B, L] (padded with -1, ylens tokens each) to
+        the padded batch xs [B, T, F] with frame counts xlens, on the device: per row ``{"score",
+        "states", "spans"}`` in encoder frames (``frame_subsampling`` input frames each), or None
+        where the transcript does not fit its frames.  A row with xlen == T is the unpadded
+        computation; a padded row is the computation training sees for it (decoding.ctc_align)."""
+        return D.ctc_align(self, xs, xlens, ys, ylens)
+
     @torch.no_grad()
     def attention(self, x):
         """liteasr/models/u2.py:163-216 (beam 10); returns the best hypothesis incl. sos."""

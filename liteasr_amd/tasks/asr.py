@@ -20,7 +20,7 @@ import torch
 from ..config import MISSING, LiteasrDataclass
 from ..dataclass.vocab import Vocab
 from ..dataset import AudioFileDataset
-from ..utils.frontend import Fbank, num_frames, speed_ratios
+from ..utils.frontend import FRAME_SHIFT, SAMPLE_RATE, Fbank, num_frames, speed_ratios
 from . import LiteasrTask, register_task
 
 logger = logging.getLogger(__name__)
@@ -123,6 +123,34 @@ class ASRTask(LiteasrTask):
         for ids in model.inference_batch(xs, xlens):
             tokens = self.vocab.lookupi(list(ids), convert=True)
             out.append("".join(tokens) if self.cfg.delimiter is None else self.cfg.delimiter.join(tokens))
+        return out
+
+    def align(self, xs, xlens, ys, ylens, model):
+        """Token timestamps through ``model.align`` (U2: CTC forced alignment on the device).  ``xs``
+        / ``xlens`` as ``inference_batch`` takes them (features, or int16 PCM that goes through the
+        task's front end first); ``ys`` (B, L) token ids padded with -1, ``ylens`` tokens each.
+
+        Returns per row ``([(token, start_s, dur_s)], score)``, or ``(None, -inf)`` for a row that
+        cannot be aligned.  Times count encoder frames from the start of the utterance: start_s =
+        first * step and dur_s = (end - first) * step with step = frame shift of the front end
+        (10 ms) x the model's ``frame_subsampling`` (4) = 0.04 s; the window length and the
+        receptive field of the subsampling convolutions are not added."""
+        if not hasattr(model, "align"):
+            raise TypeError(f"{type(model).__name__} has no align (forced alignment needs a CTC head: U2)")
+        if xs.dtype == torch.int16:
+            frames = [num_frames(int(n)) for n in xlens]
+            xs = self.frontend(xs, torch.tensor(frames, dtype=torch.int32, device=xs.device), max_frames=max(frames))
+            xlens = frames
+        step = FRAME_SHIFT / SAMPLE_RATE * model.frame_subsampling
+        ylens = [int(n) for n in ylens]
+        out = []
+        for b, rec in enumerate(model.align(xs, xlens, ys, ylens)):
+            if rec is None:
+                out.append((None, float("-inf")))
+                continue
+            tokens = self.vocab.lookupi([int(i) for i in ys[b, :ylens[b]].tolist()], convert=True)
+            out.append(([(tok, first * step, (end - first) * step) for tok, (first, end) in zip(tokens, rec["spans"])],
+                        rec["score"]))
         return out
 
     def save_model(self, model_name: str, model):
