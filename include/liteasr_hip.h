@@ -723,6 +723,40 @@ int lasr_resample_i16(const int16_t* pcm, int64_t in_stride, int B, int64_t S_in
                       const int32_t* ratios, int n_ratios, const float* taps, int64_t n_taps, int16_t* out,
                       int64_t out_stride, int64_t S_out, void* stream);
 
+/* Additive noise of task=asr on raw audio (csrc/mix.hip; the reference has none): every row mixed
+ * with up to 8 sources of a resident noise bank, each at its own host-drawn SNR.  For a row with
+ * n samples x and sources j = 0 .. count - 1 in plan order, source j the recording w of `length`
+ * samples at bank[offset], read from phase `start` and wrapped, v_j[m] = w[(start + m) mod length]:
+ *   Ex = sum_{m<n} x[m]^2,  Ev_j = sum_{m<n} v_j[m]^2   (int64, exact: the order does not matter),
+ *   g_j = (float)sqrt((double)Ex / (double)Ev_j * r_j),  r_j = 10^(-snr_j / 10) from the host
+ *     (IEEE double division and square root); g_j = 0 when Ex = 0 or Ev_j = 0,
+ *   acc = (float)x[m];  acc = fmaf(g_j, (float)v_j[m], acc) for j ascending;
+ *   y[m] = acc rounded to nearest-even and saturated to int16;  y[m] = 0 for n <= m < S.
+ *   pcm [B] rows of S int16 samples, in_stride elements apart (2-byte alignment is enough);
+ *   bank int16 [bank_len] (device): the recordings, back to back;
+ *   plan int32 [B][3] (device, host-drawn): n, first source, count of each row; the kernels clamp
+ *     n to [0, S];
+ *   sources int64 [n_src][4] (device, 8-byte aligned): offset, length, start and the bits of the
+ *     float64 r of each source; liteasr_amd.kernels.mix_plan lays both tables out;
+ *   out int16 [B] rows of S samples, out_stride elements apart, every element written.  out may
+ *     be pcm itself (the same pointer and, for B > 1, the same stride); otherwise it must not
+ *     overlap pcm.  It must not overlap the bank or the workspace;
+ *   gains fp32 [n_src] or NULL: g of every source some row's [first, first + count) holds (a source
+ *     no row holds is not written; rows that share a source leave either row's value);
+ *   ws: device scratch of at least lasr_mix_ws_bytes(B, S) bytes, 8-byte aligned (the energy
+ *     partials, nine int64 per row and 4096 samples).
+ * A source is skipped (g = 0) when its recording or phase falls outside the bank (length < 1,
+ * offset < 0, offset + length > bank_len, start outside [0, length)) or r is no finite number
+ * >= 0; all sources of a row are skipped when count is outside 0..8 or [first, first + count)
+ * leaves the table.  Nothing outside the rows and the bank is read or written whatever the plan
+ * holds.  S <= 2^29, B <= 65535.  Two launches, no atomics; a sample's bits depend on x[m], the
+ * v_j[m] and the row's gains only, not on the row's place in the batch, the strides, the
+ * alignment or whether the call is in place.  On a failed check nothing is launched. */
+int64_t lasr_mix_ws_bytes(int B, int64_t S);
+int lasr_mix_i16(const int16_t* pcm, int64_t in_stride, int B, int64_t S, const int16_t* bank,
+                 int64_t bank_len, const int32_t* plan, const int64_t* sources, int64_t n_src, int16_t* out,
+                 int64_t out_stride, float* gains, void* ws, int64_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------
  * SpecAugment (liteasr/utils/transform/spec_augment.py:14-125; applied per utterance in
  * the reference's DataLoader workers, liteasr/dataset/asr_dataset.py:118).  Replaces the

@@ -29,9 +29,17 @@ length sort, the batch budgets and the SpecAugment plan see what the model will;
 without a frame is dropped and counted like a short utterance.  The collator still reads the
 source samples with one native call and appends a ResamplePlan (source and resampled counts and
 the ratio of every row); the resampling itself runs on the device (liteasr_amd/utils/frontend.py).
+
+Additive noise (``noise``, a NoiseSpec; the train split of a raw-audio directory only) is drawn per
+step: the dataset holds the bank's index only (offset, length and directory of every noise
+recording, from the WAV headers), and the collator draws per row, from a generator of the
+dataset's own, whether it is augmented, a directory, the number of sources and per source a
+recording, a start and an SNR, and appends them as a NoisePlan, the batch's last element.  The
+mixing runs on the device, on the resampled samples when both options are on.
 """
 
 import logging
+import os
 from typing import List, Optional
 
 import numpy as np
@@ -41,7 +49,8 @@ from ..dataclass.audio_data import Audio, SpeedWavAudio, WavAudio
 from ..dataclass.sheet import AudioSheet, TextSheet
 from ..utils import wavio
 from ..utils.batchify import FrameBatch, SeqBatch
-from ..utils.frontend import ResamplePlan, num_frames, resampled_samples, speed_ratios, used_samples
+from ..utils.frontend import (ResamplePlan, draw_noise_plan, num_frames, resampled_samples, speed_ratios,
+                              used_samples)
 from ..utils.kaldiio import read_padded
 from ..utils.transform import PostProcess
 from .liteasr_dataset import LiteasrDataset
@@ -51,7 +60,7 @@ logger = logging.getLogger(__name__)
 
 class AudioFileDataset(LiteasrDataset):
     def __init__(self, split: str, data_dir: str, delimiter: Optional[str], dataset_cfg, postprocess_cfg, vocab,
-                 keep_raw=False, memory_save=False, num_mel_bins: int = 80, speed_perturb=None):
+                 keep_raw=False, memory_save=False, num_mel_bins: int = 80, speed_perturb=None, noise=None):
         super().__init__()
         if memory_save:
             raise NotImplementedError("memory_save (pickled batch dumps) is not supported")
@@ -71,6 +80,13 @@ class AudioFileDataset(LiteasrDataset):
             logger.info("{}: speed_perturb is ignored for a feats.scp directory".format(data_dir))
             self.speed = None
         self.speed_table = list(dict.fromkeys(self.speed)) if self.speed is not None else None  # the distinct ratios
+        self.noise = noise if split == "train" else None  # a NoiseSpec or None
+        if self.noise is not None and not self.wav:
+            logger.info("{}: noise is ignored for a feats.scp directory".format(data_dir))
+            self.noise = None
+        # where every noise recording lies in the bank (never the samples: workers stay light)
+        self.noise_index = self.noise.index() if self.noise is not None else None
+        self._noise_rng = None  # (pid, Generator), made in the process that collates
         short = 0
         records = list(zip(audios, texts))
         for ratio in self.speed if self.speed is not None else [None]:
@@ -124,7 +140,7 @@ class AudioFileDataset(LiteasrDataset):
         xlens = torch.tensor([s.xlen for s in batch], dtype=torch.long)
         ylens = torch.tensor([s.ylen for s in batch], dtype=torch.long)
         post = self.postprocess if (self.train and self.postprocess is not None and len(self.postprocess)) else None
-        plan = rplan = None
+        plan = rplan = nplan = None
         if post is not None and post.device_capable:
             # draw the augmentation here (same RNG order as the reference's per-utterance
             # calls); the pixels are produced on the GPU by the trainer (apply_batch)
@@ -136,6 +152,9 @@ class AudioFileDataset(LiteasrDataset):
             xs = self._collate_pcm(batch)
             if self.speed is not None:
                 rplan = self._resample_plan(batch)
+            if self.noise is not None:
+                nplan = draw_noise_plan(self._noise_generator(), self.noise, self.noise_index,
+                                        [s.samples if isinstance(s, SpeedWavAudio) else s.shape for s in batch])
         elif post is None and all(s.start is None for s in batch):
             tmax = int(xlens.max()) if B else 0
             xs = torch.empty(B, tmax, self.feat_dim, dtype=torch.float32)
@@ -151,7 +170,22 @@ class AudioFileDataset(LiteasrDataset):
             if s.ylen:
                 ys[i, : s.ylen] = torch.tensor(s.tokenids, dtype=torch.long)
         out = (xs, xlens, ys, ylens) if plan is None else (xs, xlens, ys, ylens, plan)
-        return out if rplan is None else out + (rplan,)
+        out = out if rplan is None else out + (rplan,)
+        return out if nplan is None else out + (nplan,)
+
+    def _noise_generator(self):
+        """The dataset's own generator for the noise draws, seeded from ``noise_seed`` and torch's
+        initial seed of the collating process (a DataLoader worker's follows the loader's per-epoch
+        base seed).  Python's, numpy's and torch's global streams are not touched."""
+        pid = os.getpid()
+        if self._noise_rng is None or self._noise_rng[0] != pid:
+            self._noise_rng = (pid, np.random.default_rng([self.noise.seed, torch.initial_seed() % (1 << 63)]))
+        return self._noise_rng[1]
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state["_noise_rng"] = None  # a worker makes its own
+        return state
 
     def _resample_plan(self, batch: List[SpeedWavAudio]) -> ResamplePlan:
         rows = torch.tensor([[s.shape, s.samples, self.speed_table.index(s.ratio)] for s in batch],

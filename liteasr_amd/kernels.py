@@ -1388,6 +1388,74 @@ def resample_i16(pcm, plan, ratios, taps, out=None, max_out=None):
     return out
 
 
+# Additive noise (csrc/mix.hip): up to MIX_MAX_SOURCES recordings of a resident bank per row.
+MIX_MAX_SOURCES = 8
+
+
+def mix_plan(ns, sources):
+    """The kernel's two host tables for a batch: ``ns`` the samples of every row, ``sources`` per
+    row a list of (offset, length, start, r): the recording at bank[offset : offset + length],
+    read from ``start`` and wrapped, and r = 10^(-snr / 10) as a float64.  Returns (rows int32
+    [B, 3]: n, first source, count; table int64 [n_src, 4]: offset, length, start and the bits of
+    r), the sources of the rows back to back in row order."""
+    import numpy as np
+
+    if len(ns) != len(sources):
+        raise ValueError(f"mix_plan: {len(ns)} rows, source lists for {len(sources)}")
+    rows = np.zeros((len(ns), 3), dtype=np.int32)
+    flat = []
+    for b, (n, srcs) in enumerate(zip(ns, sources)):
+        if len(srcs) > MIX_MAX_SOURCES:
+            raise ValueError(f"mix_plan: row {b} has {len(srcs)} sources, at most {MIX_MAX_SOURCES} are mixed")
+        rows[b] = (int(n), len(flat), len(srcs))
+        flat.extend(srcs)
+    table = np.zeros((len(flat), 4), dtype=np.int64)
+    if flat:
+        table[:, :3] = np.asarray([s[:3] for s in flat], dtype=np.int64)
+        table[:, 3] = np.asarray([s[3] for s in flat], dtype=np.float64).view(np.int64)
+    return rows, table
+
+
+def mix_i16(pcm, bank, rows, sources, out=None, gains=None):
+    """Rows of 16-bit PCM with noise of a resident bank mixed in at host-drawn SNRs (lasr_mix_i16):
+    ``pcm`` an int16 device tensor (B, S) with contiguous rows (any row stride), ``bank`` the
+    int16 vector of recordings on that device, ``rows`` int32 (B, 3) and ``sources`` int64
+    (n_src, 4) the device copies of ``mix_plan``.  Returns ``out``, int16 (B, S) with contiguous
+    rows, every element written: samples m >= n[b] are zero.  ``out`` None makes a new tensor;
+    ``out`` may be ``pcm`` itself (in place), otherwise it must not overlap it.  ``gains``: an
+    fp32 [n_src] device tensor that receives the gain of every source."""
+    if (pcm.dtype != torch.int16 or pcm.dim() != 2 or pcm.device.type != "cuda"
+            or (pcm.shape[1] > 1 and pcm.stride(1) != 1)):
+        raise TypeError("mix_i16: an int16 (B, S) device tensor with contiguous rows is needed")
+    B, S = pcm.shape
+    if B > 1 and S and pcm.stride(0) < S:
+        raise TypeError("mix_i16: the rows of pcm overlap")
+    if bank.dtype != torch.int16 or bank.device != pcm.device or bank.dim() != 1 or not bank.is_contiguous():
+        raise TypeError("mix_i16: bank must be a contiguous int16 vector on the device of pcm")
+    if rows.dtype != torch.int32 or rows.device != pcm.device or rows.shape != (B, 3) or not rows.is_contiguous():
+        raise TypeError("mix_i16: rows must be a contiguous int32 (B, 3) tensor on the device of pcm")
+    if (sources.dtype != torch.int64 or sources.device != pcm.device or sources.dim() != 2 or sources.shape[1] != 4
+            or not sources.is_contiguous()):
+        raise TypeError("mix_i16: sources must be a contiguous int64 (n_src, 4) tensor on the device of pcm")
+    n_src = sources.shape[0]
+    if gains is not None and (gains.dtype != torch.float32 or gains.device != pcm.device or gains.shape != (n_src,)
+                              or not gains.is_contiguous()):
+        raise TypeError("mix_i16: gains must be a contiguous fp32 [n_src] tensor on the device of pcm")
+    if out is None:
+        out = torch.empty(B, S, dtype=torch.int16, device=pcm.device)
+    elif (out.dtype != torch.int16 or out.device != pcm.device or out.dim() != 2 or out.shape[0] != B
+          or (out.shape[1] > 1 and out.stride(1) != 1) or (B > 1 and out.shape[1] and out.stride(0) < out.shape[1])):
+        raise TypeError("mix_i16: out must be an int16 (B, S) tensor with contiguous rows on the device of pcm")
+    elif out.shape[1] != S:
+        raise ValueError(f"mix_i16: out holds {out.shape[1]} samples per row, pcm {S}")
+    nbytes = N.load().lasr_mix_ws_bytes(B, S)
+    ws = torch.empty(max(nbytes // 8, 1), dtype=torch.int64, device=pcm.device)
+    N.call("lasr_mix_i16", ptr(pcm), pcm.stride(0) if B > 1 else S, B, S, ptr(bank) if bank.numel() else None,
+           bank.numel(), ptr(rows), ptr(sources) if n_src else None, n_src, ptr(out),
+           out.stride(0) if B > 1 else S, ptr(gains), ptr(ws), ws.numel() * 8, stream())
+    return out
+
+
 def scale_add(a, b, sa, sb, out):
     N.call("lasr_scale_add", ptr(a), dt(a), ptr(b), dt(b) if b is not None else 0, sa, sb,
            ptr(out), dt(out), out.numel(), stream())

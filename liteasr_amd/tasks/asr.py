@@ -6,7 +6,9 @@ and no feats.scp is raw audio: the task's front end (``task.frontend``: Kaldi fb
 computes the features on the device, in the trainer and in ``inference``.  Every other Kaldi
 fbank option is fixed at the value documented there; ``dither`` other than 0 is refused.
 ``task.frontend.speed_perturb`` (a list of speed factors) applies to the train split of a raw-audio
-directory only: valid and test splits, ``inference`` and feats.scp directories ignore it."""
+directory only: valid and test splits, ``inference`` and feats.scp directories ignore it.  So does
+``task.frontend.noise`` (a list of noise directories: additive noise mixed in on the device, at
+SNRs drawn per utterance; the ``noise_*`` keys beside it)."""
 
 import inspect
 import logging
@@ -20,7 +22,8 @@ import torch
 from ..config import MISSING, LiteasrDataclass
 from ..dataclass.vocab import Vocab
 from ..dataset import AudioFileDataset
-from ..utils.frontend import FRAME_SHIFT, SAMPLE_RATE, Fbank, num_frames, speed_ratios
+from ..utils.frontend import (FRAME_SHIFT, SAMPLE_RATE, Fbank, NoiseSpec, check_noise_options, num_frames,
+                              speed_ratios)
 from . import LiteasrTask, register_task
 
 logger = logging.getLogger(__name__)
@@ -36,6 +39,15 @@ class FrontendConfig(LiteasrDataclass):
     # speed factors of the train split, e.g. [0.9, 1.0, 1.1]: one copy of every utterance per factor,
     # resampled on the device in front of the fbank kernel (None: off)
     speed_perturb: Optional[List[float]] = field(default=None)
+    # additive noise of the train split, mixed on the device in front of the fbank kernel: wav.scp
+    # directories of 16 kHz 16-bit mono recordings, kept resident in HBM (None: off)
+    noise: Optional[List[str]] = field(default=None)
+    noise_prob: float = field(default=0.5)  # probability that an utterance is augmented
+    # SNR range in dB and range of the number of sources: one pair for all directories, or one per directory
+    noise_snr: List[float] = field(default_factory=lambda: [0.0, 15.0])
+    noise_sources: List[int] = field(default_factory=lambda: [1, 1])  # each value in 1..8
+    noise_seed: int = field(default=0)  # seed of the augmentation generator
+    noise_max_mb: int = field(default=2048)  # cap on the resident bank
 
 
 @dataclass
@@ -56,9 +68,26 @@ def _frontend_get(cfg):
     return fe.get if isinstance(fe, dict) else lambda k, d=None: getattr(fe, k, d)
 
 
+def _noise_of(get) -> Optional[NoiseSpec]:
+    """``frontend.noise*`` as a checked NoiseSpec, None with the option off; the other keys are
+    checked either way."""
+    def val(key, default):
+        v = get(key, None)
+        return default if v is None else v
+
+    opts = dict(prob=val("noise_prob", 0.5), snr=list(val("noise_snr", [0.0, 15.0])),
+                sources=list(val("noise_sources", [1, 1])), seed=val("noise_seed", 0), max_mb=val("noise_max_mb", 2048))
+    dirs = get("noise", None)
+    if not dirs:
+        check_noise_options(**opts)
+        return None
+    return NoiseSpec([dirs] if isinstance(dirs, str) else list(dirs), **opts)
+
+
 def _frontend_of(cfg) -> Fbank:
     get = _frontend_get(cfg)
-    return Fbank(num_mel_bins=get("num_mel_bins", 80), cmvn=get("cmvn", None), dither=float(get("dither", 0.0) or 0.0))
+    return Fbank(num_mel_bins=get("num_mel_bins", 80), cmvn=get("cmvn", None), dither=float(get("dither", 0.0) or 0.0),
+                 noise=_noise_of(get))
 
 
 @register_task("asr", dataclass=ASRConfig)
@@ -74,6 +103,7 @@ class ASRTask(LiteasrTask):
         sp = _frontend_get(cfg)("speed_perturb", None)
         self.speed_perturb = [float(s) for s in sp] if sp else None
         speed_ratios(self.speed_perturb)  # a factor the resampler does not take is refused here
+        self.noise = self.frontend.noise.spec if self.frontend.noise is not None else None
 
     def load_dataset(self, split: str, data_dir: Union[str, list], dataset_cfg=None, postprocess_cfg=None,
                      memory_save: bool = False):
@@ -84,7 +114,8 @@ class ASRTask(LiteasrTask):
             return AudioFileDataset(split=split, data_dir=d, delimiter=self.cfg.delimiter, dataset_cfg=dataset_cfg,
                                     postprocess_cfg=postprocess_cfg, vocab=self.vocab, keep_raw=split == "test",
                                     memory_save=memory_save, num_mel_bins=self.frontend.num_mel_bins,
-                                    speed_perturb=self.speed_perturb if split == "train" else None)
+                                    speed_perturb=self.speed_perturb if split == "train" else None,
+                                    noise=self.noise if split == "train" else None)
 
         if isinstance(data_dir, str):
             self.datasets[split] = one(data_dir)

@@ -18,6 +18,13 @@ front of it, on the device too: the collator still delivers the source int16 bat
 ResamplePlan, and ``lasr_resample_i16`` (csrc/resample.hip) makes the int16 batch the fbank kernel
 reads: Kaldi's LinearResample (Hann-windowed sinc, filter width 6, roll-off 0.99), rounded and
 saturated to 16 bits like the WAV file an offline ``speed`` + ``rate`` pipeline writes.
+
+Additive noise (``frontend.noise``, a list of wav.scp directories of 16 kHz 16-bit mono recordings,
+MUSAN-style; the train split only; the reference has none) runs between the two, in place on the
+int16 batch: the recordings stay resident in HBM as one int16 bank (NoiseMixer), the collator draws
+per utterance whether it is augmented, a directory, the number of sources and per source a
+recording, a start and an SNR (NoisePlan), and ``lasr_mix_i16`` (csrc/mix.hip) scales every source
+to its SNR against the utterance's own energy and adds it, rounded and saturated to 16 bits.
 """
 
 import numpy as np
@@ -133,13 +140,201 @@ class SpeedPerturb(object):
         return K.resample_i16(pcm, plan.rows.to(pcm.device), table, taps, out=out, max_out=plan.max_out)
 
 
+def _ranges(name, values, ndirs, integer):
+    """``values`` (two numbers, or two per directory) as one (lo, hi) per directory."""
+    vals = None if values is None or isinstance(values, (str, int, float)) else list(values)
+    if (vals is None or any(isinstance(v, str) for v in vals) or len(vals) < 2 or len(vals) % 2
+            or (ndirs is not None and len(vals) not in (2, 2 * ndirs))):
+        raise ValueError(f"frontend.{name} must hold two values, or two per noise directory, got {values!r}")
+    pairs = [(vals[i], vals[i + 1]) for i in range(0, len(vals), 2)]
+    for lo, hi in pairs:
+        if integer and (int(lo) != lo or int(hi) != hi or not 1 <= lo <= 8 or not 1 <= hi <= 8):
+            raise ValueError(f"frontend.{name}: source counts must be integers in 1..8, got {values!r}")
+        if not lo <= hi:  # a NaN fails too
+            raise ValueError(f"frontend.{name}: the lower bound {lo} is above the upper bound {hi}")
+    pairs = [(int(lo), int(hi)) if integer else (float(lo), float(hi)) for lo, hi in pairs]
+    return pairs * ndirs if ndirs is not None and len(pairs) == 1 else pairs
+
+
+class NoiseIndex(object):
+    """Where every recording of the noise directories lies in the bank: ``paths``, ``offsets`` and
+    ``lengths`` (samples, int64) in the order of the directories and of their wav.scp lines,
+    ``dir_of`` the directory of each and ``by_dir`` the recordings of each directory.  No sample is
+    read for it: the lengths come from the WAV headers."""
+
+    __slots__ = ("paths", "offsets", "lengths", "dir_of", "by_dir", "total")
+
+    def __init__(self, dirs, max_mb):
+        import os
+
+        from ..dataclass.sheet import AudioSheet
+        from . import wavio
+
+        self.paths, lengths, dir_of, self.by_dir = [], [], [], []
+        for d, data_dir in enumerate(dirs):
+            scp = os.path.join(data_dir, "wav.scp")
+            if not os.path.isfile(scp):
+                raise FileNotFoundError(f"frontend.noise: wav.scp not found in {data_dir}")
+            first = len(self.paths)
+            with open(scp, "r") as f:
+                for _, path in AudioSheet._wav_entries(ln for ln in f if ln.strip()):
+                    info = wavio.probe(path)
+                    if (info.rate, info.bits, info.channels) != (SAMPLE_RATE, 16, 1) or info.frames < 1:
+                        raise ValueError(f"frontend.noise: {path} is {info.rate} Hz, {info.bits} bits, {info.channels} "
+                                         f"channel(s), {info.frames} samples; 16 kHz 16-bit mono recordings are needed")
+                    self.paths.append(path)
+                    lengths.append(info.frames)
+                    dir_of.append(d)
+            if len(self.paths) == first:
+                raise ValueError(f"frontend.noise: {data_dir} lists no recording")
+            self.by_dir.append(np.arange(first, len(self.paths), dtype=np.int64))
+        self.lengths = np.asarray(lengths, dtype=np.int64)
+        self.offsets = np.concatenate([[0], np.cumsum(self.lengths)[:-1]]).astype(np.int64)
+        self.dir_of = np.asarray(dir_of, dtype=np.int32)
+        self.total = int(self.lengths.sum())
+        if 2 * self.total > int(max_mb) * (1 << 20):
+            raise ValueError(f"frontend.noise: the {len(self.paths)} recordings hold {self.total} samples, "
+                             f"{2 * self.total / (1 << 20):.1f} MB, above frontend.noise_max_mb = {max_mb}; raise the "
+                             "cap or list fewer recordings (nothing is left out silently)")
+
+
+class NoiseSpec(object):
+    """``frontend.noise*`` checked: the directories, the probability that an utterance is augmented,
+    per directory its SNR range in dB and its range of source counts, the seed and the cap on the
+    resident bank.  ``index()`` is the NoiseIndex over the directories, made on first use and kept
+    (the train dataset and the NoiseMixer share it)."""
+
+    def __init__(self, dirs, prob=0.5, snr=(0.0, 15.0), sources=(1, 1), seed=0, max_mb=2048):
+        self.dirs = [dirs] if isinstance(dirs, str) else [str(d) for d in dirs]
+        if not self.dirs:
+            raise ValueError("frontend.noise lists no directory")
+        self.prob, self.seed, self.max_mb = check_noise_options(prob, snr, sources, seed, max_mb, len(self.dirs))
+        self.snr, self.sources = _ranges("noise_snr", snr, len(self.dirs), False), _ranges(
+            "noise_sources", sources, len(self.dirs), True)
+        self._index = None
+
+    def index(self) -> NoiseIndex:
+        if self._index is None:
+            self._index = NoiseIndex(self.dirs, self.max_mb)
+        return self._index
+
+
+def check_noise_options(prob, snr, sources, seed, max_mb, ndirs=None):
+    """Refuses a probability outside [0, 1], lo > hi, source counts outside 1..8, a wrong list
+    length, a negative seed or cap; returns (prob, seed, max_mb)."""
+    prob = float(prob)
+    if not 0.0 <= prob <= 1.0:
+        raise ValueError(f"frontend.noise_prob must lie in [0, 1], got {prob}")
+    _ranges("noise_snr", snr, ndirs, False)
+    _ranges("noise_sources", sources, ndirs, True)
+    if int(seed) != seed or int(seed) < 0:
+        raise ValueError(f"frontend.noise_seed must be an integer >= 0, got {seed!r}")
+    if int(max_mb) != max_mb or int(max_mb) < 0:
+        raise ValueError(f"frontend.noise_max_mb must be an integer >= 0, got {max_mb!r}")
+    return prob, int(seed), int(max_mb)
+
+
+class NoisePlan(object):
+    """What the collator of a noise-augmented dataset adds to its batch, as the last element (after
+    a ResamplePlan if there is one): the host tables of ``kernels.mix_plan``, ``rows`` int32 (B, 3)
+    (samples, first source and source count of every row; the samples are those after speed
+    perturbation) and ``sources`` int64 (n, 4) (offset, length and start in the bank, the bits of
+    r = 10^(-snr / 10)), and ``snr`` the drawn dB values per row.  Trainer._features takes it off
+    the batch again."""
+
+    __slots__ = ("rows", "sources", "snr")
+
+    def __init__(self, rows, sources, snr):
+        self.rows, self.sources, self.snr = rows, sources, snr
+
+
+def draw_noise_plan(rng, spec: NoiseSpec, index: NoiseIndex, ns) -> NoisePlan:
+    """One NoisePlan for rows of ``ns`` samples from the numpy Generator ``rng``.  Per row, in this
+    order: a uniform number (augmented when below ``noise_prob``; nothing else is drawn
+    otherwise), a directory, the source count in the directory's range, then per source a
+    recording of the directory, a start in [0, length) and an SNR in the directory's range."""
+    import torch
+
+    from ..kernels import mix_plan
+
+    srcs, snrs = [], []
+    for _ in ns:
+        row, row_snr = [], []
+        if rng.random() < spec.prob:
+            d = int(rng.integers(len(spec.dirs)))
+            lo, hi = spec.sources[d]
+            for _ in range(int(rng.integers(lo, hi + 1))):
+                rec = int(index.by_dir[d][int(rng.integers(len(index.by_dir[d])))])
+                start = int(rng.integers(int(index.lengths[rec])))
+                snr = float(rng.uniform(*spec.snr[d]))
+                row.append((int(index.offsets[rec]), int(index.lengths[rec]), start, 10.0 ** (-snr / 10.0)))
+                row_snr.append(snr)
+        srcs.append(row)
+        snrs.append(row_snr)
+    rows, table = mix_plan([int(n) for n in ns], srcs)
+    return NoisePlan(torch.from_numpy(rows), torch.from_numpy(table), snrs)
+
+
+class NoiseMixer(object):
+    """Additive noise of the train split (``task.frontend.noise``): owns the resident bank, every
+    recording of the noise directories back to back as int16 on the device.  On first use it reads
+    them with the native WAV reader into one pinned buffer and uploads that with one copy; a call
+    mixes the rows of an int16 (B, S) batch with the sources of a NoisePlan (``lasr_mix_i16``)."""
+
+    def __init__(self, spec: NoiseSpec):
+        self.spec = spec
+        self._dev = {}
+
+    @property
+    def index(self) -> NoiseIndex:
+        return self.spec.index()
+
+    def read_bank(self, pin: bool = False):
+        """The bank on the host, an int16 vector of ``index.total`` samples."""
+        import torch
+
+        from . import wavio
+
+        idx = self.index
+        bank = torch.empty(idx.total, dtype=torch.int16, pin_memory=pin)
+        arr = bank.numpy()
+        for path, off, n in zip(idx.paths, idx.offsets.tolist(), idx.lengths.tolist()):
+            got = wavio.read_into(path, arr[off:off + n])
+            if got != n:
+                raise IOError(f"{path}: {got} samples on disk, its header says {n}")
+        return bank
+
+    def bank_on(self, device):
+        import torch
+
+        key = torch.device(device)
+        if key.index is None:
+            key = torch.device(key.type, torch.cuda.current_device())
+        if key not in self._dev:
+            self._dev[key] = self.read_bank(pin=True).to(key, non_blocking=True)
+            torch.cuda.current_stream(key).synchronize()  # the pinned buffer goes away here
+        return self._dev[key]
+
+    def __call__(self, pcm, plan: NoisePlan, out=None, gains=None):
+        from .. import kernels as K
+
+        return K.mix_i16(pcm, self.bank_on(pcm.device), plan.rows.to(pcm.device), plan.sources.to(pcm.device),
+                         out=out, gains=gains)
+
+    def __repr__(self):
+        s = self.spec
+        return f"NoiseMixer(dirs={s.dirs!r}, prob={s.prob}, snr={s.snr}, sources={s.sources})"
+
+
 class Fbank(object):
     """int16 (B, S) PCM on the device + frame counts -> fp32 (B, T, F) features, zero-padded.
     ``speed``: the speed perturbation that runs in front of it on training batches that carry a
-    ResamplePlan."""
+    ResamplePlan.  ``noise``: the NoiseMixer of ``frontend.noise`` (None: off), which runs between
+    the two on batches that carry a NoisePlan."""
 
-    def __init__(self, num_mel_bins: int = 80, cmvn: str = None, dither: float = 0.0):
+    def __init__(self, num_mel_bins: int = 80, cmvn: str = None, dither: float = 0.0, noise: "NoiseSpec" = None):
         self.speed = SpeedPerturb()
+        self.noise = NoiseMixer(noise) if noise is not None else None
         if dither != 0:
             raise NotImplementedError("frontend.dither: dithering (a device RNG in the front end) is not supported")
         self.num_mel_bins = int(num_mel_bins)

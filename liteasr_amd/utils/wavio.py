@@ -55,6 +55,16 @@ def read(path: str, start: int = 0, count: Optional[int] = None):
     return out, got.value
 
 
+def read_into(path: str, out: np.ndarray, start: int = 0) -> int:
+    """Samples [start, start + len(out)) into ``out`` (int16, C-contiguous; a slice of a pinned
+    buffer, say); returns how many were there, the rest is zero."""
+    assert out.dtype == np.int16 and out.ndim == 1 and out.flags.c_contiguous
+    got = C.c_int64()
+    _kio._check(lib().lasr_wav_read_i16(path.encode(), start, out.shape[0], out.ctypes.data_as(C.c_void_p),
+                                        C.byref(got)))
+    return got.value
+
+
 def read_batch(paths: Sequence[str], starts: Sequence[int], count: int, out: Optional[np.ndarray] = None,
                nthreads: int = 0):
     """The window [starts[i], starts[i] + count) of every file into an int16 [n, count] array
