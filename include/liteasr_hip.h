@@ -757,6 +757,46 @@ int lasr_mix_i16(const int16_t* pcm, int64_t in_stride, int B, int64_t S, const 
                  int64_t bank_len, const int32_t* plan, const int64_t* sources, int64_t n_src, int16_t* out,
                  int64_t out_stride, float* gains, void* ws, int64_t ws_bytes, void* stream);
 
+/* Room reverberation of task=asr on raw audio (csrc/reverb.hip; the reference has none): every row
+ * convolved with a room impulse response (RIR) of a resident int16 bank: Kaldi's wav-reverberate
+ * --shift-output=true --normalize-output=true with the input's duration kept.  For a row of n
+ * samples x and the RIR h of L int16 samples at bank[offset] whose peak index is p (the first index
+ * of its largest sample, found on the host):
+ *   c[m] = sum_{k<L} (h[k] 2^-15) x[m + p - k],  0 <= m < n,  x = 0 outside [0, n)   (fp32): the
+ *     first p samples of the full convolution and its tail past n are dropped;
+ *   Ex = sum x^2 (int64, exact);  Ec = sum_{m<n} c[m]^2 in double over the fp32 values c, in a
+ *     fixed order: per block of 2048 samples (per lane in index order, the wave's tree, the waves
+ *     ascending), then the blocks ascending;
+ *   g = (float)sqrt((double)Ex / Ec);  g = 0 when Ex = 0 or Ec = 0;
+ *   y[m] = g c[m] rounded to nearest-even and saturated to int16;  y[m] = 0 for n <= m < S.
+ *   pcm [B] rows of S int16 samples, in_stride elements apart (2-byte alignment is enough);
+ *   bank int16 [bank_len] (device): the RIRs, back to back;
+ *   plan int32 [B][2] (device, host-drawn): n and the RIR index of each row; the kernels clamp n to
+ *     [0, S]; index -1 names no RIR: the row is copied bit for bit and zero-padded;
+ *   rirs int64 [n_rir][3] (device, 8-byte aligned): offset, length and peak of each RIR;
+ *   tab fp32 [8192] (device, 8-byte aligned): exp(-2 pi i m / 4096), m < 4096, as (re, im) pairs,
+ *     computed in float64 (liteasr_amd.kernels.reverb_tables);
+ *   out int16 [B] rows of S samples, out_stride elements apart, every element written.  out may
+ *     be pcm itself (the same pointer and, for B > 1, the same stride); otherwise it must not
+ *     overlap pcm.  It must not overlap the bank or the workspace;
+ *   gains fp32 [B] or NULL: g of every row, 1.0 for a copied row, 0 for a refused one;
+ *   ws: device scratch of at least lasr_reverb_ws_bytes(B, S, Lmax) bytes, 16-byte aligned, Lmax
+ *     the longest RIR the call may meet (the spectra, the fp32 convolution and two partial sums
+ *     per row and block).  ws_bytes tells the entry for how many partitions per RIR it was made.
+ * An RIR is refused, and the row comes out zero, when its index is outside the table (and not -1),
+ * offset / length leaves the bank, length is outside 1..65536 or needs more partitions than the
+ * workspace was made for, or p is outside [0, L).  Nothing outside the rows, the bank and the
+ * workspace is read or written whatever the plan holds.  S <= 2^29, B <= 65535.
+ * Uniformly partitioned overlap-save at the fixed block size 2048 (4096-point real transforms,
+ * partitions accumulated in fp32 with the partition index ascending); three launches, no atomics.
+ * A sample's bits depend on x[0..n), h, p and m only, not on the row's place in the batch, B, S,
+ * the strides, the alignment, Lmax or whether the call is in place.  On a failed check nothing is
+ * launched. */
+int64_t lasr_reverb_ws_bytes(int B, int64_t S, int64_t Lmax);
+int lasr_reverb_i16(const int16_t* pcm, int64_t in_stride, int B, int64_t S, const int16_t* bank,
+                    int64_t bank_len, const int32_t* plan, const int64_t* rirs, int64_t n_rir, const float* tab,
+                    int16_t* out, int64_t out_stride, float* gains, void* ws, int64_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------
  * SpecAugment (liteasr/utils/transform/spec_augment.py:14-125; applied per utterance in
  * the reference's DataLoader workers, liteasr/dataset/asr_dataset.py:118).  Replaces the

@@ -222,6 +222,8 @@ SIGNATURES = {
     "lasr_resample_i16": [_p, _l, _i, _l, _p, _p, _i, _p, _l, _p, _l, _l, _p],
     "lasr_mix_ws_bytes": [_i, _l],
     "lasr_mix_i16": [_p, _l, _i, _l, _p, _l, _p, _p, _l, _p, _l, _p, _p, _l, _p],
+    "lasr_reverb_ws_bytes": [_i, _l, _l],
+    "lasr_reverb_i16": [_p, _l, _i, _l, _p, _l, _p, _p, _l, _p, _p, _l, _p, _p, _l, _p],
     "lasr_sumsq_nparts": [_l],
     "lasr_sumsq_partial": [_p, _l, _p, _l, _p],
     "lasr_adam_step": [_p, _p, _i, _p, _p, _p, _l, _p, _i, _p, _f, _i, _f, _f, _f, _f, _f, _f,
@@ -260,6 +262,7 @@ SIGNATURES = {
     "lasr_w2v_contrast_bwd": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p, _l, _p],
 }
 _RESTYPES = {"lasr_last_error": C.c_char_p, "lasr_spec_augment_ws_bytes": C.c_int64, "lasr_mix_ws_bytes": C.c_int64,
+             "lasr_reverb_ws_bytes": C.c_int64,
              "lasr_rnnt_search_workspace": C.c_int64, "lasr_rescore_workspace": C.c_int64,
              "lasr_rescore_workspace_batch": C.c_int64, "lasr_ctc_align_workspace": C.c_int64,
              "lasr_conv2_dx_w1_workspace": C.c_int64, "lasr_attn_split_work": C.c_int64,

@@ -36,6 +36,11 @@ recording, from the WAV headers), and the collator draws per row, from a generat
 dataset's own, whether it is augmented, a directory, the number of sources and per source a
 recording, a start and an SNR, and appends them as a NoisePlan, the batch's last element.  The
 mixing runs on the device, on the resampled samples when both options are on.
+
+Room reverberation (``rir``, a RirSpec; the train split of a raw-audio directory only) is drawn per
+step in the same way, from a generator of its own: the dataset holds the RIR bank's index only, the
+collator draws per utterance whether it is reverberated, a directory and an RIR, and appends a
+ReverbPlan after the ResamplePlan and before the NoisePlan.
 """
 
 import logging
@@ -49,8 +54,8 @@ from ..dataclass.audio_data import Audio, SpeedWavAudio, WavAudio
 from ..dataclass.sheet import AudioSheet, TextSheet
 from ..utils import wavio
 from ..utils.batchify import FrameBatch, SeqBatch
-from ..utils.frontend import (ResamplePlan, draw_noise_plan, num_frames, resampled_samples, speed_ratios,
-                              used_samples)
+from ..utils.frontend import (ResamplePlan, draw_noise_plan, draw_reverb_plan, num_frames, resampled_samples,
+                              speed_ratios, used_samples)
 from ..utils.kaldiio import read_padded
 from ..utils.transform import PostProcess
 from .liteasr_dataset import LiteasrDataset
@@ -60,7 +65,8 @@ logger = logging.getLogger(__name__)
 
 class AudioFileDataset(LiteasrDataset):
     def __init__(self, split: str, data_dir: str, delimiter: Optional[str], dataset_cfg, postprocess_cfg, vocab,
-                 keep_raw=False, memory_save=False, num_mel_bins: int = 80, speed_perturb=None, noise=None):
+                 keep_raw=False, memory_save=False, num_mel_bins: int = 80, speed_perturb=None, noise=None,
+                 rir=None):
         super().__init__()
         if memory_save:
             raise NotImplementedError("memory_save (pickled batch dumps) is not supported")
@@ -87,6 +93,12 @@ class AudioFileDataset(LiteasrDataset):
         # where every noise recording lies in the bank (never the samples: workers stay light)
         self.noise_index = self.noise.index() if self.noise is not None else None
         self._noise_rng = None  # (pid, Generator), made in the process that collates
+        self.rir = rir if split == "train" else None  # a RirSpec or None
+        if self.rir is not None and not self.wav:
+            logger.info("{}: rir is ignored for a feats.scp directory".format(data_dir))
+            self.rir = None
+        self.rir_index = self.rir.index() if self.rir is not None else None  # never the samples
+        self._rir_rng = None  # (pid, Generator), as for the noise
         short = 0
         records = list(zip(audios, texts))
         for ratio in self.speed if self.speed is not None else [None]:
@@ -140,7 +152,7 @@ class AudioFileDataset(LiteasrDataset):
         xlens = torch.tensor([s.xlen for s in batch], dtype=torch.long)
         ylens = torch.tensor([s.ylen for s in batch], dtype=torch.long)
         post = self.postprocess if (self.train and self.postprocess is not None and len(self.postprocess)) else None
-        plan = rplan = nplan = None
+        plan = rplan = vplan = nplan = None
         if post is not None and post.device_capable:
             # draw the augmentation here (same RNG order as the reference's per-utterance
             # calls); the pixels are produced on the GPU by the trainer (apply_batch)
@@ -152,9 +164,11 @@ class AudioFileDataset(LiteasrDataset):
             xs = self._collate_pcm(batch)
             if self.speed is not None:
                 rplan = self._resample_plan(batch)
+            ns = [s.samples if isinstance(s, SpeedWavAudio) else s.shape for s in batch]
+            if self.rir is not None:
+                vplan = draw_reverb_plan(self._rir_generator(), self.rir, self.rir_index, ns)
             if self.noise is not None:
-                nplan = draw_noise_plan(self._noise_generator(), self.noise, self.noise_index,
-                                        [s.samples if isinstance(s, SpeedWavAudio) else s.shape for s in batch])
+                nplan = draw_noise_plan(self._noise_generator(), self.noise, self.noise_index, ns)
         elif post is None and all(s.start is None for s in batch):
             tmax = int(xlens.max()) if B else 0
             xs = torch.empty(B, tmax, self.feat_dim, dtype=torch.float32)
@@ -171,6 +185,7 @@ class AudioFileDataset(LiteasrDataset):
                 ys[i, : s.ylen] = torch.tensor(s.tokenids, dtype=torch.long)
         out = (xs, xlens, ys, ylens) if plan is None else (xs, xlens, ys, ylens, plan)
         out = out if rplan is None else out + (rplan,)
+        out = out if vplan is None else out + (vplan,)
         return out if nplan is None else out + (nplan,)
 
     def _noise_generator(self):
@@ -182,9 +197,17 @@ class AudioFileDataset(LiteasrDataset):
             self._noise_rng = (pid, np.random.default_rng([self.noise.seed, torch.initial_seed() % (1 << 63)]))
         return self._noise_rng[1]
 
+    def _rir_generator(self):
+        """The dataset's own generator for the reverberation draws, made like the noise's from
+        ``rir_seed``; the trailing 1 keeps the two streams apart at equal seeds."""
+        pid = os.getpid()
+        if self._rir_rng is None or self._rir_rng[0] != pid:
+            self._rir_rng = (pid, np.random.default_rng([self.rir.seed, torch.initial_seed() % (1 << 63), 1]))
+        return self._rir_rng[1]
+
     def __getstate__(self):
         state = dict(self.__dict__)
-        state["_noise_rng"] = None  # a worker makes its own
+        state["_noise_rng"] = state["_rir_rng"] = None  # a worker makes its own
         return state
 
     def _resample_plan(self, batch: List[SpeedWavAudio]) -> ResamplePlan:

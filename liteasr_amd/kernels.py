@@ -1456,6 +1456,84 @@ def mix_i16(pcm, bank, rows, sources, out=None, gains=None):
     return out
 
 
+# Room reverberation (csrc/reverb.hip): uniformly partitioned overlap-save at one fixed block size.
+REVERB_BLOCK, REVERB_MAX_TAPS = 2048, 65536
+
+
+def reverb_tables():
+    """The kernel's twiddle table, computed in float64 on the host: float32 [4 REVERB_BLOCK], the
+    complex numbers exp(-2 pi i m / (2 REVERB_BLOCK)), m < 2 REVERB_BLOCK, as (re, im) pairs."""
+    import numpy as np
+
+    ang = -2.0 * np.pi * np.arange(2 * REVERB_BLOCK, dtype=np.float64) / (2 * REVERB_BLOCK)
+    return np.stack([np.cos(ang), np.sin(ang)], axis=1).astype(np.float32).reshape(-1)
+
+
+def reverb_plan(ns, rir_ids):
+    """The kernel's host table for a batch, int32 [B, 2]: per row its samples ``ns[b]`` and the
+    index ``rir_ids[b]`` of its RIR in the ``rirs`` table, -1 for a row that is only copied."""
+    import numpy as np
+
+    if len(ns) != len(rir_ids):
+        raise ValueError(f"reverb_plan: {len(ns)} rows, RIR indices for {len(rir_ids)}")
+    rows = np.zeros((len(ns), 2), dtype=np.int32)
+    for b, (n, i) in enumerate(zip(ns, rir_ids)):
+        rows[b] = (int(n), int(i))
+    return rows
+
+
+_reverb_tab = {}
+
+
+def reverb_i16(pcm, bank, rows, rirs, out=None, gains=None, max_taps=None):
+    """Rows of 16-bit PCM convolved with room impulse responses of a resident bank, shifted to the
+    RIR's peak, cut to the row's own samples and scaled back to the row's energy (lasr_reverb_i16):
+    ``pcm`` an int16 device tensor (B, S) with contiguous rows (any row stride), ``bank`` the int16
+    vector of RIRs on that device, ``rows`` int32 (B, 2) the device copy of ``reverb_plan`` and
+    ``rirs`` int64 (n_rir, 3) on the device: offset, length and peak index of every RIR.  Returns
+    ``out``, int16 (B, S) with contiguous rows, every element written: samples m >= n[b] are zero.
+    ``out`` None makes a new tensor; ``out`` may be ``pcm`` itself (in place), otherwise it must
+    not overlap it.  ``gains``: an fp32 [B] device tensor that receives the gain of every row (1
+    for a copied row).  ``max_taps``: the caller's host-side bound on the lengths in ``rirs`` (a
+    longer RIR gives a zero row); None reads it back from the device, one synchronisation.  The
+    workspace is made here."""
+    if (pcm.dtype != torch.int16 or pcm.dim() != 2 or pcm.device.type != "cuda"
+            or (pcm.shape[1] > 1 and pcm.stride(1) != 1)):
+        raise TypeError("reverb_i16: an int16 (B, S) device tensor with contiguous rows is needed")
+    B, S = pcm.shape
+    if B > 1 and S and pcm.stride(0) < S:
+        raise TypeError("reverb_i16: the rows of pcm overlap")
+    if bank.dtype != torch.int16 or bank.device != pcm.device or bank.dim() != 1 or not bank.is_contiguous():
+        raise TypeError("reverb_i16: bank must be a contiguous int16 vector on the device of pcm")
+    if rows.dtype != torch.int32 or rows.device != pcm.device or rows.shape != (B, 2) or not rows.is_contiguous():
+        raise TypeError("reverb_i16: rows must be a contiguous int32 (B, 2) tensor on the device of pcm")
+    if (rirs.dtype != torch.int64 or rirs.device != pcm.device or rirs.dim() != 2 or rirs.shape[1] != 3
+            or not rirs.is_contiguous()):
+        raise TypeError("reverb_i16: rirs must be a contiguous int64 (n_rir, 3) tensor on the device of pcm")
+    n_rir = rirs.shape[0]
+    if gains is not None and (gains.dtype != torch.float32 or gains.device != pcm.device or gains.shape != (B,)
+                              or not gains.is_contiguous()):
+        raise TypeError("reverb_i16: gains must be a contiguous fp32 [B] tensor on the device of pcm")
+    if out is None:
+        out = torch.empty(B, S, dtype=torch.int16, device=pcm.device)
+    elif (out.dtype != torch.int16 or out.device != pcm.device or out.dim() != 2 or out.shape[0] != B
+          or (out.shape[1] > 1 and out.stride(1) != 1) or (B > 1 and out.shape[1] and out.stride(0) < out.shape[1])):
+        raise TypeError("reverb_i16: out must be an int16 (B, S) tensor with contiguous rows on the device of pcm")
+    elif out.shape[1] != S:
+        raise ValueError(f"reverb_i16: out holds {out.shape[1]} samples per row, pcm {S}")
+    if max_taps is None:
+        max_taps = int(rirs[:, 1].max()) if n_rir else 1
+    max_taps = min(max(int(max_taps), 1), REVERB_MAX_TAPS)
+    if pcm.device not in _reverb_tab:
+        _reverb_tab[pcm.device] = torch.from_numpy(reverb_tables()).to(pcm.device)
+    nbytes = N.load().lasr_reverb_ws_bytes(B, S, max_taps)
+    ws = torch.empty(max(nbytes // 8, 2), dtype=torch.int64, device=pcm.device)
+    N.call("lasr_reverb_i16", ptr(pcm), pcm.stride(0) if B > 1 else S, B, S, ptr(bank) if bank.numel() else None,
+           bank.numel(), ptr(rows), ptr(rirs) if n_rir else None, n_rir, ptr(_reverb_tab[pcm.device]), ptr(out),
+           out.stride(0) if B > 1 else S, ptr(gains), ptr(ws), ws.numel() * 8, stream())
+    return out
+
+
 def scale_add(a, b, sa, sb, out):
     N.call("lasr_scale_add", ptr(a), dt(a), ptr(b), dt(b) if b is not None else 0, sa, sb,
            ptr(out), dt(out), out.numel(), stream())

@@ -8,7 +8,9 @@ fbank option is fixed at the value documented there; ``dither`` other than 0 is 
 ``task.frontend.speed_perturb`` (a list of speed factors) applies to the train split of a raw-audio
 directory only: valid and test splits, ``inference`` and feats.scp directories ignore it.  So does
 ``task.frontend.noise`` (a list of noise directories: additive noise mixed in on the device, at
-SNRs drawn per utterance; the ``noise_*`` keys beside it)."""
+SNRs drawn per utterance; the ``noise_*`` keys beside it) and ``task.frontend.rir`` (a list of
+directories of room impulse responses: reverberation convolved on the device; ``rir_prob``,
+``rir_seed`` and ``rir_max_mb`` beside it)."""
 
 import inspect
 import logging
@@ -22,8 +24,8 @@ import torch
 from ..config import MISSING, LiteasrDataclass
 from ..dataclass.vocab import Vocab
 from ..dataset import AudioFileDataset
-from ..utils.frontend import (FRAME_SHIFT, SAMPLE_RATE, Fbank, NoiseSpec, check_noise_options, num_frames,
-                              speed_ratios)
+from ..utils.frontend import (FRAME_SHIFT, SAMPLE_RATE, Fbank, NoiseSpec, RirSpec, check_noise_options,
+                              check_rir_options, num_frames, speed_ratios)
 from . import LiteasrTask, register_task
 
 logger = logging.getLogger(__name__)
@@ -48,6 +50,13 @@ class FrontendConfig(LiteasrDataclass):
     noise_sources: List[int] = field(default_factory=lambda: [1, 1])  # each value in 1..8
     noise_seed: int = field(default=0)  # seed of the augmentation generator
     noise_max_mb: int = field(default=2048)  # cap on the resident bank
+    # room reverberation of the train split, convolved on the device between the resampler and the
+    # mixer: wav.scp directories of 16 kHz 16-bit mono impulse responses of at most 65536 samples,
+    # kept resident in HBM (None: off)
+    rir: Optional[List[str]] = field(default=None)
+    rir_prob: float = field(default=0.5)  # probability that an utterance is reverberated
+    rir_seed: int = field(default=0)  # seed of the generator of the reverberation draws
+    rir_max_mb: int = field(default=512)  # cap on the resident bank
 
 
 @dataclass
@@ -84,10 +93,25 @@ def _noise_of(get) -> Optional[NoiseSpec]:
     return NoiseSpec([dirs] if isinstance(dirs, str) else list(dirs), **opts)
 
 
+def _rir_of(get) -> Optional[RirSpec]:
+    """``frontend.rir*`` as a checked RirSpec, None with the option off; the other keys are checked
+    either way."""
+    def val(key, default):
+        v = get(key, None)
+        return default if v is None else v
+
+    opts = dict(prob=val("rir_prob", 0.5), seed=val("rir_seed", 0), max_mb=val("rir_max_mb", 512))
+    dirs = get("rir", None)
+    if not dirs:
+        check_rir_options(**opts)
+        return None
+    return RirSpec([dirs] if isinstance(dirs, str) else list(dirs), **opts)
+
+
 def _frontend_of(cfg) -> Fbank:
     get = _frontend_get(cfg)
     return Fbank(num_mel_bins=get("num_mel_bins", 80), cmvn=get("cmvn", None), dither=float(get("dither", 0.0) or 0.0),
-                 noise=_noise_of(get))
+                 noise=_noise_of(get), rir=_rir_of(get))
 
 
 @register_task("asr", dataclass=ASRConfig)
@@ -104,6 +128,7 @@ class ASRTask(LiteasrTask):
         self.speed_perturb = [float(s) for s in sp] if sp else None
         speed_ratios(self.speed_perturb)  # a factor the resampler does not take is refused here
         self.noise = self.frontend.noise.spec if self.frontend.noise is not None else None
+        self.rir = self.frontend.reverb.spec if self.frontend.reverb is not None else None
 
     def load_dataset(self, split: str, data_dir: Union[str, list], dataset_cfg=None, postprocess_cfg=None,
                      memory_save: bool = False):
@@ -115,7 +140,8 @@ class ASRTask(LiteasrTask):
                                     postprocess_cfg=postprocess_cfg, vocab=self.vocab, keep_raw=split == "test",
                                     memory_save=memory_save, num_mel_bins=self.frontend.num_mel_bins,
                                     speed_perturb=self.speed_perturb if split == "train" else None,
-                                    noise=self.noise if split == "train" else None)
+                                    noise=self.noise if split == "train" else None,
+                                    rir=self.rir if split == "train" else None)
 
         if isinstance(data_dir, str):
             self.datasets[split] = one(data_dir)

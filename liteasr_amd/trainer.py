@@ -18,7 +18,7 @@ from torch.utils.data.dataloader import DataLoader
 from torch.utils.data.distributed import DistributedSampler
 
 from .utils.data_loader import EpochDataLoader
-from .utils.frontend import NoisePlan, ResamplePlan
+from .utils.frontend import NoisePlan, ResamplePlan, ReverbPlan
 from .utils.trigger import EventManager, Trigger
 
 logger = logging.getLogger(__name__)
@@ -118,10 +118,14 @@ class Trainer(object):
         no lengths) is only copied.  A batch of a speed-perturbed dataset ends with a ResamplePlan:
         its int16 rows are resampled on the device first, each by its own speed factor.  A batch of a
         noise-augmented dataset ends with a NoisePlan (after the ResamplePlan, if both ride along):
-        the noise is mixed into the (resampled) int16 rows in place: resample, mix, fbank."""
-        rplan = nplan = None
+        the noise is mixed into the (resampled) int16 rows in place.  A ReverbPlan rides between the
+        two: the rows are convolved with their room impulse responses in place before the noise is
+        mixed in: resample, reverb, mix, fbank."""
+        rplan = vplan = nplan = None
         if isinstance(batch, (tuple, list)) and len(batch) and isinstance(batch[-1], NoisePlan):
             nplan, batch = batch[-1], tuple(batch[:-1])
+        if isinstance(batch, (tuple, list)) and len(batch) and isinstance(batch[-1], ReverbPlan):
+            vplan, batch = batch[-1], tuple(batch[:-1])
         if isinstance(batch, (tuple, list)) and len(batch) and isinstance(batch[-1], ResamplePlan):
             rplan, batch = batch[-1], tuple(batch[:-1])
         raw = (isinstance(batch, (tuple, list)) and len(batch) >= 2 and torch.is_tensor(batch[0])
@@ -129,14 +133,20 @@ class Trainer(object):
         tmax = int(batch[1].max()) if raw and batch[1].numel() else 0  # on the host: no read-back later
         own = raw and batch[0].device.type == "cpu"  # the device copy below is this call's own
         batch = to_device(batch, self.device)
-        if (rplan is not None or nplan is not None) and not raw:
-            raise TypeError("a ResamplePlan or NoisePlan rides on raw-audio batches only")
+        if (rplan is not None or vplan is not None or nplan is not None) and not raw:
+            raise TypeError("a ResamplePlan, ReverbPlan or NoisePlan rides on raw-audio batches only")
         if raw:
             pcm = batch[0] if rplan is None else self.task.frontend.speed(batch[0], rplan)
+            own = own or rplan is not None  # the resampler's output is this call's own too
+            if vplan is not None:
+                if getattr(self.task.frontend, "reverb", None) is None:
+                    raise TypeError("a ReverbPlan needs task.frontend.rir")
+                pcm = self.task.frontend.reverb(pcm, vplan, out=pcm if own else None)
+                own = True
             if nplan is not None:
                 if self.task.frontend.noise is None:
                     raise TypeError("a NoisePlan needs task.frontend.noise")
-                pcm = self.task.frontend.noise(pcm, nplan, out=pcm if own or rplan is not None else None)
+                pcm = self.task.frontend.noise(pcm, nplan, out=pcm if own else None)
             batch = (self.task.frontend(pcm, batch[1], max_frames=tmax),) + tuple(batch[1:])
         return batch
 

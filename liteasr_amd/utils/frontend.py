@@ -25,6 +25,17 @@ int16 batch: the recordings stay resident in HBM as one int16 bank (NoiseMixer),
 per utterance whether it is augmented, a directory, the number of sources and per source a
 recording, a start and an SNR (NoisePlan), and ``lasr_mix_i16`` (csrc/mix.hip) scales every source
 to its SNR against the utterance's own energy and adds it, rounded and saturated to 16 bits.
+
+Room reverberation (``frontend.rir``, a list of wav.scp directories of 16 kHz 16-bit mono room
+impulse responses of at most 65536 samples; the train split only; the reference has none) runs
+between the resampler and the mixer, in place too: the RIRs stay resident in HBM as one int16 bank
+with the index of every RIR's peak (Reverberator), the collator draws per utterance whether it is
+reverberated, a directory and an RIR of it (ReverbPlan), and ``lasr_reverb_i16`` (csrc/reverb.hip)
+convolves, shifts to the peak, keeps the utterance's duration and energy, rounds and saturates:
+Kaldi's ``wav-reverberate --shift-output=true --normalize-output=true``.  With noise on too, the
+SNR is taken against the reverberated utterance, whose energy is the clean one's up to rounding;
+Kaldi takes the early-reverberation energy there and reverberates point-source noises with RIRs of
+their own: neither is done here.
 """
 
 import numpy as np
@@ -160,11 +171,12 @@ class NoiseIndex(object):
     """Where every recording of the noise directories lies in the bank: ``paths``, ``offsets`` and
     ``lengths`` (samples, int64) in the order of the directories and of their wav.scp lines,
     ``dir_of`` the directory of each and ``by_dir`` the recordings of each directory.  No sample is
-    read for it: the lengths come from the WAV headers."""
+    read for it: the lengths come from the WAV headers.  ``key`` names the option in the messages
+    (``frontend.noise`` or ``frontend.rir``); ``max_frames``: the longest recording taken."""
 
     __slots__ = ("paths", "offsets", "lengths", "dir_of", "by_dir", "total")
 
-    def __init__(self, dirs, max_mb):
+    def __init__(self, dirs, max_mb, key="noise", max_frames=None):
         import os
 
         from ..dataclass.sheet import AudioSheet
@@ -174,27 +186,30 @@ class NoiseIndex(object):
         for d, data_dir in enumerate(dirs):
             scp = os.path.join(data_dir, "wav.scp")
             if not os.path.isfile(scp):
-                raise FileNotFoundError(f"frontend.noise: wav.scp not found in {data_dir}")
+                raise FileNotFoundError(f"frontend.{key}: wav.scp not found in {data_dir}")
             first = len(self.paths)
             with open(scp, "r") as f:
                 for _, path in AudioSheet._wav_entries(ln for ln in f if ln.strip()):
                     info = wavio.probe(path)
                     if (info.rate, info.bits, info.channels) != (SAMPLE_RATE, 16, 1) or info.frames < 1:
-                        raise ValueError(f"frontend.noise: {path} is {info.rate} Hz, {info.bits} bits, {info.channels} "
+                        raise ValueError(f"frontend.{key}: {path} is {info.rate} Hz, {info.bits} bits, {info.channels} "
                                          f"channel(s), {info.frames} samples; 16 kHz 16-bit mono recordings are needed")
+                    if max_frames is not None and info.frames > max_frames:
+                        raise ValueError(f"frontend.{key}: {path} holds {info.frames} samples, at most {max_frames} "
+                                         "are taken (nothing is truncated silently)")
                     self.paths.append(path)
                     lengths.append(info.frames)
                     dir_of.append(d)
             if len(self.paths) == first:
-                raise ValueError(f"frontend.noise: {data_dir} lists no recording")
+                raise ValueError(f"frontend.{key}: {data_dir} lists no recording")
             self.by_dir.append(np.arange(first, len(self.paths), dtype=np.int64))
         self.lengths = np.asarray(lengths, dtype=np.int64)
         self.offsets = np.concatenate([[0], np.cumsum(self.lengths)[:-1]]).astype(np.int64)
         self.dir_of = np.asarray(dir_of, dtype=np.int32)
         self.total = int(self.lengths.sum())
         if 2 * self.total > int(max_mb) * (1 << 20):
-            raise ValueError(f"frontend.noise: the {len(self.paths)} recordings hold {self.total} samples, "
-                             f"{2 * self.total / (1 << 20):.1f} MB, above frontend.noise_max_mb = {max_mb}; raise the "
+            raise ValueError(f"frontend.{key}: the {len(self.paths)} recordings hold {self.total} samples, "
+                             f"{2 * self.total / (1 << 20):.1f} MB, above frontend.{key}_max_mb = {max_mb}; raise the "
                              "cap or list fewer recordings (nothing is left out silently)")
 
 
@@ -326,15 +341,143 @@ class NoiseMixer(object):
         return f"NoiseMixer(dirs={s.dirs!r}, prob={s.prob}, snr={s.snr}, sources={s.sources})"
 
 
+RIR_MAX_SAMPLES = 65536
+
+
+def check_rir_options(prob, seed, max_mb):
+    """Refuses a probability outside [0, 1], a negative seed or cap; returns (prob, seed, max_mb)."""
+    if isinstance(prob, str) or not 0.0 <= float(prob) <= 1.0:  # a NaN fails too
+        raise ValueError(f"frontend.rir_prob must lie in [0, 1], got {prob!r}")
+    if isinstance(seed, str) or int(seed) != seed or int(seed) < 0:
+        raise ValueError(f"frontend.rir_seed must be an integer >= 0, got {seed!r}")
+    if isinstance(max_mb, str) or int(max_mb) != max_mb or int(max_mb) < 0:
+        raise ValueError(f"frontend.rir_max_mb must be an integer >= 0, got {max_mb!r}")
+    return float(prob), int(seed), int(max_mb)
+
+
+class RirSpec(object):
+    """``frontend.rir*`` checked: the directories, the probability that an utterance is
+    reverberated, the seed and the cap on the resident bank.  ``index()`` is the NoiseIndex over
+    the directories (16 kHz 16-bit mono, at most 65536 samples each), made on first use and kept
+    (the train dataset and the Reverberator share it)."""
+
+    def __init__(self, dirs, prob=0.5, seed=0, max_mb=512):
+        self.dirs = [dirs] if isinstance(dirs, str) else [str(d) for d in dirs]
+        if not self.dirs:
+            raise ValueError("frontend.rir lists no directory")
+        self.prob, self.seed, self.max_mb = check_rir_options(prob, seed, max_mb)
+        self._index = None
+
+    def index(self) -> NoiseIndex:
+        if self._index is None:
+            self._index = NoiseIndex(self.dirs, self.max_mb, key="rir", max_frames=RIR_MAX_SAMPLES)
+        return self._index
+
+
+class ReverbPlan(object):
+    """What the collator of a reverberated dataset adds to its batch (after a ResamplePlan, before
+    a NoisePlan): ``rows`` int32 (B, 2) on the host, the table of ``kernels.reverb_plan``: per row
+    its samples (those after speed perturbation) and the index of its RIR in the bank's table, -1
+    for a row that stays as it is.  Trainer._features takes it off the batch again."""
+
+    __slots__ = ("rows",)
+
+    def __init__(self, rows):
+        self.rows = rows
+
+
+def draw_reverb_plan(rng, spec: RirSpec, index: NoiseIndex, ns) -> ReverbPlan:
+    """One ReverbPlan for rows of ``ns`` samples from the numpy Generator ``rng``.  Per row, in this
+    order: a uniform number (reverberated when below ``rir_prob``; nothing else is drawn
+    otherwise), a directory, an RIR of the directory."""
+    import torch
+
+    from ..kernels import reverb_plan
+
+    ids = []
+    for _ in ns:
+        rir = -1
+        if rng.random() < spec.prob:
+            d = int(rng.integers(len(spec.dirs)))
+            rir = int(index.by_dir[d][int(rng.integers(len(index.by_dir[d])))])
+        ids.append(rir)
+    return ReverbPlan(torch.from_numpy(reverb_plan([int(n) for n in ns], ids)))
+
+
+class Reverberator(object):
+    """Room reverberation of the train split (``task.frontend.rir``): owns the resident bank, every
+    RIR of the directories back to back as int16 on the device, and the int64 table (offset, length,
+    peak) of the RIRs.  On first use it reads them with the native WAV reader into one pinned buffer,
+    finds every peak (the first index of the largest sample; an all-zero recording is refused) and
+    uploads the bank with one copy; a call reverberates the rows of an int16 (B, S) batch as a
+    ReverbPlan says (``lasr_reverb_i16``)."""
+
+    def __init__(self, spec: RirSpec):
+        self.spec = spec
+        self._dev = {}
+
+    @property
+    def index(self) -> NoiseIndex:
+        return self.spec.index()
+
+    def read_bank(self, pin: bool = False):
+        """(bank, rirs) on the host: the int16 vector of ``index.total`` samples and the int64
+        (n_rir, 3) table of offset, length and peak."""
+        import torch
+
+        from . import wavio
+
+        idx = self.index
+        bank = torch.empty(idx.total, dtype=torch.int16, pin_memory=pin)
+        arr = bank.numpy()
+        table = np.zeros((len(idx.paths), 3), dtype=np.int64)
+        for i, (path, off, n) in enumerate(zip(idx.paths, idx.offsets.tolist(), idx.lengths.tolist())):
+            got = wavio.read_into(path, arr[off:off + n])
+            if got != n:
+                raise IOError(f"{path}: {got} samples on disk, its header says {n}")
+            h = arr[off:off + n]
+            peak = int(np.argmax(h))  # the first index of the largest sample
+            if h[peak] == 0 and not h.any():
+                raise ValueError(f"frontend.rir: {path} holds {n} samples, all zero: no impulse response")
+            table[i] = (off, n, peak)
+        return bank, torch.from_numpy(table)
+
+    def tables_on(self, device):
+        import torch
+
+        key = torch.device(device)
+        if key.index is None:
+            key = torch.device(key.type, torch.cuda.current_device())
+        if key not in self._dev:
+            bank, table = self.read_bank(pin=True)
+            self._dev[key] = (bank.to(key, non_blocking=True), table.to(key))
+            torch.cuda.current_stream(key).synchronize()  # the pinned buffer goes away here
+        return self._dev[key]
+
+    def __call__(self, pcm, plan: ReverbPlan, out=None, gains=None):
+        from .. import kernels as K
+
+        bank, table = self.tables_on(pcm.device)
+        return K.reverb_i16(pcm, bank, plan.rows.to(pcm.device), table, out=out, gains=gains,
+                            max_taps=int(self.index.lengths.max()))
+
+    def __repr__(self):
+        return f"Reverberator(dirs={self.spec.dirs!r}, prob={self.spec.prob})"
+
+
 class Fbank(object):
     """int16 (B, S) PCM on the device + frame counts -> fp32 (B, T, F) features, zero-padded.
     ``speed``: the speed perturbation that runs in front of it on training batches that carry a
     ResamplePlan.  ``noise``: the NoiseMixer of ``frontend.noise`` (None: off), which runs between
-    the two on batches that carry a NoisePlan."""
+    the two on batches that carry a NoisePlan.  ``reverb``: the Reverberator of ``frontend.rir``
+    (None: off), which runs between the resampler and the mixer on batches that carry a
+    ReverbPlan."""
 
-    def __init__(self, num_mel_bins: int = 80, cmvn: str = None, dither: float = 0.0, noise: "NoiseSpec" = None):
+    def __init__(self, num_mel_bins: int = 80, cmvn: str = None, dither: float = 0.0, noise: "NoiseSpec" = None,
+                 rir: "RirSpec" = None):
         self.speed = SpeedPerturb()
         self.noise = NoiseMixer(noise) if noise is not None else None
+        self.reverb = Reverberator(rir) if rir is not None else None
         if dither != 0:
             raise NotImplementedError("frontend.dither: dithering (a device RNG in the front end) is not supported")
         self.num_mel_bins = int(num_mel_bins)

@@ -76,3 +76,25 @@ def synthetic_wav_dir(root: str, lengths, seed: int = 0, tokens: str = "abcdefgh
             scp.write(f"utt{j:04d} {paths[j % len(paths)]}\n")
             txt.write(f"utt{j:04d} {texts[j % len(paths)]}\n")
     return root
+
+
+def synthetic_rir_dir(root: str, lengths, seed: int = 0) -> str:
+    """A wav.scp directory ``root`` of synthetic room impulse responses, one per entry of ``lengths``
+    (samples): Gaussian noise under an exponential decay (60 dB over the recording, at a tenth of
+    the direct path's level) with one unit direct-path peak, 32767, within the first 20 samples.
+    Returns ``root``."""
+    import os
+
+    import numpy as np
+
+    rng = np.random.default_rng(seed)
+    os.makedirs(os.path.join(root, "wav"), exist_ok=True)
+    with open(os.path.join(root, "wav.scp"), "w") as scp:
+        for i, n in enumerate(lengths):
+            n = int(n)
+            h = 0.1 * rng.standard_normal(n) * 10.0 ** (-3.0 * np.arange(n) / max(n, 1))
+            h[int(rng.integers(min(n, 20)))] = 1.0
+            path = os.path.join(root, "wav", f"rir{i:04d}.wav")
+            write_wav(path, np.clip(np.round(h * 32767), -32767, 32767).astype(np.int16))
+            scp.write(f"rir{i:04d} {path}\n")
+    return root
